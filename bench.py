@@ -12,11 +12,15 @@ and rank r solves its contiguous slice shard_range(batch x N, r, N).  Per-GPU wo
 --batch defaults to 4096 at N = 1 (configs[2], the headline) and to 8192 per GPU at N > 1 (configs[3]: N = 8
 is the 65 536-sample batch).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python bench.py --gpus N ...                        (spawns N rank processes itself when WORLD_SIZE is unset)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line (value = samples/s summed over ranks, samples = solve+gradient units).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the untimed side measurements
+(configs[1] forward-solve rates, the IFT gradient mode, the configs[4] moving-gate figure, the CPU baseline; for
+--workload moving the diagnostics pass).  --dump-outputs DIR saves what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -50,9 +54,17 @@ def parse(argv=None):
                          "episodes over the GPUs)")
     ap.add_argument("--cpu-sample", type=int, default=1024, help="samples timed on the host oracle, all cores (rank 0, N=1)")
     ap.add_argument("--cpu-sample-1core", type=int, default=48, help="samples timed on the host oracle, one core")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed side measurements: rl (N = 1): configs[1] "
+                         "ocp_solve rates, IFT rate, configs[4] moving-gate figure, CPU baseline; moving: the "
+                         "diagnostics pass (IPM iterations, kernel time, restoration counters)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the untimed side measurements (configs[1] ocp_solve rate, IFT rate)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: skip the GPU side measurements (configs[1] ocp_solve rate, IFT rate, configs[4])")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps save what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all: a fixed seeded sample of the rows beyond that, listed in "
+                         "rows.npy); with N > 1 every rank saves its shard as DIR/<name>.rank<r>.npy")
     ap.add_argument("--seed", type=int, default=1000, help="seed of the one synthetic batch all ranks slice")
     ap.add_argument("--workload", choices=("rl", "moving"), default="rl",
                     help="rl: configs[2]/[3] sol_gradient RL step (default, the headline metric); "
@@ -167,6 +179,38 @@ def cpu_baseline(n_samples: int, n_1core: int):
                       f"value_1core: {n_1core} samples on one thread, {d1:.1f} s; configs[1]: {n1} forward solves on "
                       f"one thread ({d2:.1f} s) and the 1024-solve batch on {threads} threads ({d3:.1f} s); "
                       f"configs[0]: the seed-0 single solve on one thread"}
+
+
+DUMP_BYTES = 60 * 2 ** 20   # --dump-outputs: bytes per rank (the 64 MB limit less headroom for the .npy headers)
+
+
+def dump_outputs(dirname, per_row, whole, rank, world):
+    """--dump-outputs: save the arrays of the last timed step as DIR/<name>.npy (DIR/<name>.rank<r>.npy when
+    world > 1).  ``per_row``: name -> tensor whose first axis is this rank's batch row; ``whole``: name -> tensor saved
+    as it is.  Floating arrays keep float32 / float64, anything else (statuses) is saved as float64.  When the
+    arrays exceed DUMP_BYTES, the same seeded sample of rows is kept of every per-row array and its (sorted) row
+    numbers are saved as ``rows``."""
+    def host(v):
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+    os.makedirs(dirname, exist_ok=True)
+    whole = {k: host(v) for k, v in whole.items()}
+    n_rows = len(next(iter(per_row.values())))
+    row_bytes = sum(int(np.prod(v.shape[1:])) * (4 if "float32" in str(v.dtype) else 8) for v in per_row.values()) + 8
+    keep = (DUMP_BYTES - sum(a.nbytes for a in whole.values())) // row_bytes
+    rows = None
+    if keep < n_rows:
+        rows = np.sort(np.random.RandomState(0).choice(n_rows, size=int(keep), replace=False))
+        whole["rows"] = rows.astype(np.float64)
+    for k, v in per_row.items():
+        if rows is not None:   # sampled where the array lives: only the kept rows cross to the host
+            import torch
+            v = v[rows] if isinstance(v, np.ndarray) else v[torch.as_tensor(rows, device=v.device)]
+        whole[k] = host(v)
+    sfx = f".rank{rank}" if world > 1 else ""
+    for k, a in whole.items():
+        np.save(os.path.join(dirname, f"{k}{sfx}.npy"), a)
 
 
 STATUS = {0: "solved", 1: "acceptable", 2: "max_iter", 3: "ls_fail", 4: "nonfinite", 5: "tiny_step", 6: "reg_fail",
@@ -305,10 +349,12 @@ class StubEngine:
 
 
 def moving_episodes(torch, dev, samples, noise, plant_steps, groups, net, stub, steps=1, warmup=1, barrier=None,
-                    engines=None):
+                    engines=None, keep=None):
     """Run the moving-gate episodes (main.py:44-116) `steps` times after `warmup` short runs: the episodes in `groups`
     contiguous groups, each with its own solver context, HIP stream and host thread (one group's get_input launch
-    tail overlaps another group's work).  Returns (MPC solves per run, seconds of the timed runs, engine of group 0)."""
+    tail overlaps another group's work).  Returns (MPC solves per run, seconds of the timed runs, engine of group 0).
+    ``keep``: a list that receives the last timed run's results, one run_episodes_device dict per group in episode
+    order (--dump-outputs)."""
     from learningagileflight_se3_amd import moving_gate as MG
     from learningagileflight_se3_amd.rl_step import shard_range
     own = engines is None   # engines passed in stay open (the caller's)
@@ -339,7 +385,8 @@ def moving_episodes(torch, dev, samples, noise, plant_steps, groups, net, stub, 
 
     def episode(st):   # episode state, gate kinematics, DNN2 and plant on the device
         if G == 1:
-            return MG.run_episodes_device(engs[0], net, samples, noise[:, :max(st, 1)], steps=st)
+            r = MG.run_episodes_device(engs[0], net, samples, noise[:, :max(st, 1)], steps=st)
+            return {"solves": r["solves"], "groups": [r]}
         res, errs = [None] * G, []
 
         def run(g):
@@ -356,7 +403,7 @@ def moving_episodes(torch, dev, samples, noise, plant_steps, groups, net, stub, 
             t.join()
         if errs:
             raise errs[0]
-        return {"solves": sum(r["solves"] for r in res)}
+        return {"solves": sum(r["solves"] for r in res), "groups": res}
 
     for _ in range(warmup):
         episode(MG.CTRL_EVERY)
@@ -364,13 +411,16 @@ def moving_episodes(torch, dev, samples, noise, plant_steps, groups, net, stub, 
     if barrier:
         barrier()
     t0 = time.perf_counter()
-    solves = 0
+    solves, last = 0, None
     for _ in range(steps):
-        solves += episode(plant_steps)["solves"]
+        last = episode(plant_steps)
+        solves += last["solves"]
     sync()
     if barrier:
         barrier()
     dt = time.perf_counter() - t0
+    if keep is not None and last is not None:
+        keep.extend(last["groups"])
     for q in qs:
         q.close()
     if own:
@@ -427,8 +477,9 @@ def bench_moving(args, torch, dist, world, rank, dev):
     B = hi - lo
     samples, noise, net = moving_inputs(torch, dev, n_total, lo, hi, args.plant_steps, args.seed)
     barrier = dist.barrier if world > 1 else None
+    last = []   # the last timed run's results, one dict per episode group
     solves, dt, eng, G = moving_episodes(torch, dev, samples, noise, args.plant_steps, args.moving_groups, net, stub,
-                                         steps=args.steps, warmup=args.warmup, barrier=barrier)
+                                         steps=args.steps, warmup=args.warmup, barrier=barrier, keep=last)
     solves *= args.steps
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -439,37 +490,45 @@ def bench_moving(args, torch, dist, world, rank, dev):
         solves_all = int(n.item())
     else:
         solves_all = solves
-    # untimed diagnostics pass: IPM iterations, get_input kernel time and statuses per MPC solve
-    cnts = []
-    diag = MG.run_episodes_device(eng, net, samples, noise[:, :max(args.plant_steps, 1)], steps=args.plant_steps,
-                                  counters=cnts)
-    st_all = diag["status"].cpu().numpy().reshape(-1)
-    n_diag = max(diag["solves"], 1)
-    if rank == 0:
-        print(json.dumps({
-            "metric": "MPC solves/sec (moving-gate receding horizon, 50-step horizon, configs[4])",
-            "value": round(solves_all / dt, 3), "unit": "MPC solves/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True,
-            "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f64",
-            "data": ("STUB ENGINE (harness test, no solve: every rate here is meaningless)" if stub else
-                     ("REHEARSAL: ranks share GPUs (--share-gpu), not a scaling measurement; "
-                      if getattr(args, "share_gpu", False) else "") +
-                     "synthetic episodes (seeded nn_sample + gate.move noise); the reference's trained DNN2 (nn3_1.pth)"),
-            "config": {"workload": f"main.py moving gate: per episode {args.plant_steps} plant steps (dt 0.01; "
-                                   "main.py runs 500), traversal-time fixed point on DNN2 every step, get_input "
-                                   "every 10 steps",
-                       "episodes_per_gpu": B, "global_episodes": n_total, "plant_steps": args.plant_steps,
-                       "horizon": 50, "parallelism": f"dp{world}", "backend": args.backend if world > 1 else None,
-                       "engine": "stub" if stub else "hip",
-                       "groups_per_gpu": G, "grouping": "contiguous episode groups, one solver context + HIP stream + "
-                                                        "host thread each (launch tails overlap)"},
+    if args.dump_outputs:
+        # what a caller of the timed run receives: plant states (B, steps + 1, 13), traversal times (B, steps) and
+        # the get_input statuses (B, steps / 10), the groups joined in episode order
+        dump_outputs(args.dump_outputs, {k: torch.cat([r[k] for r in last]) for k in ("states", "t", "status")}, {},
+                     rank, world)
+    st_all = torch.cat([r["status"] for r in last]).cpu().numpy().reshape(-1)   # last timed run
+    res = {
+        "metric": "MPC solves/sec (moving-gate receding horizon, 50-step horizon, configs[4])",
+        "value": round(solves_all / dt, 3), "unit": "MPC solves/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True,
+        "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f64",
+        "data": ("STUB ENGINE (harness test, no solve: every rate here is meaningless)" if stub else
+                 ("REHEARSAL: ranks share GPUs (--share-gpu), not a scaling measurement; "
+                  if getattr(args, "share_gpu", False) else "") +
+                 "synthetic episodes (seeded nn_sample + gate.move noise); the reference's trained DNN2 (nn3_1.pth)"),
+        "config": {"workload": f"main.py moving gate: per episode {args.plant_steps} plant steps (dt 0.01; "
+                               "main.py runs 500), traversal-time fixed point on DNN2 every step, get_input "
+                               "every 10 steps",
+                   "episodes_per_gpu": B, "global_episodes": n_total, "plant_steps": args.plant_steps,
+                   "horizon": 50, "parallelism": f"dp{world}", "backend": args.backend if world > 1 else None,
+                   "engine": "stub" if stub else "hip",
+                   "groups_per_gpu": G, "grouping": "contiguous episode groups, one solver context + HIP stream + "
+                                                    "host thread each (launch tails overlap)"},
+        "status_hist": {STATUS.get(int(k), str(int(k))): int(v)
+                        for k, v in zip(*np.unique(st_all[st_all >= 0], return_counts=True))}}
+    if args.full:
+        # untimed diagnostics pass: IPM iterations, get_input kernel time and restoration counters per MPC solve
+        cnts = []
+        diag = MG.run_episodes_device(eng, net, samples, noise[:, :max(args.plant_steps, 1)], steps=args.plant_steps,
+                                      counters=cnts)
+        n_diag = max(diag["solves"], 1)
+        res.update({
             "ipm_iterations_per_solve": round(sum(c["iterations"] for c in cnts) / n_diag, 2),
             "get_input_kernel_ms": round(float(np.mean([c["kernel_ms"] for c in cnts])), 3) if cnts else None,
-            "status_hist": {STATUS.get(int(k), str(int(k))): int(v)
-                            for k, v in zip(*np.unique(st_all[st_all >= 0], return_counts=True))},
             "restoration": {"entries": int(sum(c["resto_entries"] for c in cnts)),
                             "returns": int(sum(c["resto_returns"] for c in cnts)),
-                            "scope": "diagnostics pass (all MPC solves of the B x plant_steps episodes)"}}), file=RESULT_OUT, flush=True)
+                            "scope": "diagnostics pass (all MPC solves of the B x plant_steps episodes)"}})
+    if rank == 0:
+        print(json.dumps(res), file=RESULT_OUT, flush=True)
 
 
 # the result line's stream: the process's stdout as it was at start.  A rank process points its fd 1 at stderr
@@ -569,17 +628,17 @@ def bench_rl(args, torch, dist, world, rank, dev):
     def step():
         t0 = time.perf_counter()
         # hot path (GPU); last_counters below waits for it and raises on a lost probe task (device error word)
-        out8, _, st9 = eng.sol_gradient(ini, goal, gate, dnn, want_rewards=True, verify=False)
+        out8, R9, st9 = eng.sol_gradient(ini, goal, gate, dnn, want_rewards=True, verify=False)
         t1 = time.perf_counter()
-        step.status = st9
+        step.status, step.rewards = st9, R9
         ms = eng.last_kernel_ms()
         cnt = eng.last_counters()
         step.resto = eng.last_resto_counters()
         t2 = time.perf_counter()
         if graphed:
-            train_graph(out8)                                  # the same step replayed from its HIP graphs
+            step.loss = train_graph(out8)                      # the same step replayed from its HIP graphs
         else:
-            train_step(net, opt, inputs, out8, world)          # myloss backward + RCCL all-reduce + Adam
+            step.loss = train_step(net, opt, inputs, out8, world)   # myloss backward + RCCL all-reduce + Adam
         t3 = time.perf_counter()
         seg["launch"].append(t1 - t0)
         seg["wait_kernel"].append(t2 - t1)
@@ -618,6 +677,12 @@ def bench_rl(args, torch, dist, world, rank, dev):
     dt = time.perf_counter() - t0
     if args.dump_out8:
         np.save(f"{args.dump_out8}.rank{rank}.npy", out8.detach().cpu().numpy())
+    if args.dump_outputs:
+        # what a caller of the timed step receives: sol_gradient's out8 / rewards / statuses of this rank's shard,
+        # this rank's myloss value and the DNN1 parameters after the step's Adam update
+        dump_outputs(args.dump_outputs, {"out8": out8, "rewards9": step.rewards, "status9": step.status},
+                     {"loss": step.loss.reshape(1),
+                      "dnn1_params": torch.cat([p.detach().reshape(-1) for p in net.parameters()])}, rank, world)
     # replicas must hold identical DNN1 parameters after the all-reduced steps
     csum = torch.cat([p.detach().reshape(-1).double() for p in net.parameters()]).sum()
     iters_t = torch.tensor([float(np.sum(iters)), float(Bl)], dtype=torch.float64, device=dev)
@@ -705,7 +770,7 @@ def bench_rl(args, torch, dist, world, rank, dev):
                             "scope": "last timed step's launch"},
             "roofline": rf,
         })
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             from learningagileflight_se3_amd.engine import Engine
             eng_b = Engine(device=dev)
             try:
@@ -713,7 +778,7 @@ def bench_rl(args, torch, dist, world, rank, dev):
             finally:
                 eng_b.close()
             res.update(moving_side_figure(torch, dev))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.cpu_sample_1core)
     print(json.dumps(res), file=RESULT_OUT, flush=True)
 

@@ -86,3 +86,48 @@ def test_moving_two_rank_launcher_matches_one_rank():
     assert two["value"] * two["ms_per_step"] / 1e3 == pytest.approx(per_run, rel=1e-3)
     assert one["value"] * one["ms_per_step"] / 1e3 == pytest.approx(per_run, rel=1e-3)
     assert two["status_hist"] == {"solved": 4 * 2} and one["status_hist"] == {"solved": 8 * 2}   # rank 0's episodes
+
+
+def _dumped(d):
+    import numpy as np
+    return {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_dump_outputs_and_steps(tmp_path):
+    """--dump-outputs DIR saves the last timed step's arrays as float .npy files, identical from run to run with the
+    same arguments; --steps sets the number of timed steps (the DNN1 parameters move with every step) and the line
+    carries ms_per_step; the side measurements stay out of a run without --full."""
+    import numpy as np
+    common = ["--gpus", "1", "--engine", "stub", "--batch", "8", "--warmup", "1"]
+    a, b, c = (str(tmp_path / n) for n in "abc")
+    la = _line(_run(common + ["--steps", "2", "--dump-outputs", a]))
+    _line(_run(common + ["--steps", "2", "--dump-outputs", b]))
+    lc = _line(_run(common + ["--steps", "3", "--dump-outputs", c]))
+    da, db, dc = _dumped(a), _dumped(b), _dumped(c)
+    assert set(da) == {"out8.npy", "rewards9.npy", "status9.npy", "loss.npy", "dnn1_params.npy"}
+    assert da["out8.npy"].shape == (8, 8) and da["rewards9.npy"].shape == (8, 9) and da["status9.npy"].shape == (8, 9)
+    for k, v in da.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+        assert np.array_equal(v, db[k]), k
+    assert sum(v.nbytes for v in da.values()) <= 64 * 2 ** 20
+    assert la["steps"] == 2 and lc["steps"] == 3 and la["ms_per_step"] > 0 and lc["ms_per_step"] > 0
+    assert np.array_equal(da["out8.npy"], dc["out8.npy"])                  # open loop: the same solve every step
+    assert not np.array_equal(da["dnn1_params.npy"], dc["dnn1_params.npy"])   # one more Adam step
+    assert "cpu_baseline" not in la and "ocp_solve_per_s" not in la
+
+
+def test_dump_outputs_sample_is_seeded(tmp_path):
+    """Arrays beyond the byte limit are cut to one seeded sample of rows, the same rows of every per-row array."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    n = 3 * bench.DUMP_BYTES // (2 * 8 * 33)
+    x = np.arange(n * 32, dtype=np.float64).reshape(n, 32)
+    for d in ("p", "q"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "i": np.arange(n, dtype=np.int32)}, {"w": np.ones(3, np.float32)}, 0, 1)
+    p, q = _dumped(str(tmp_path / "p")), _dumped(str(tmp_path / "q"))
+    assert set(p) == {"x.npy", "i.npy", "w.npy", "rows.npy"} and all(np.array_equal(p[k], q[k]) for k in p)
+    rows = p["rows.npy"].astype(np.int64)
+    assert 0 < rows.size < n and np.all(np.diff(rows) > 0)
+    assert np.array_equal(p["i.npy"], rows.astype(np.float64)) and np.array_equal(p["x.npy"], x[rows])
+    assert sum(os.path.getsize(os.path.join(str(tmp_path / "p"), f)) for f in p) <= 64 * 2 ** 20

@@ -31,6 +31,9 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 L=$GRAFT_REPO_ROOT/learningagileflight_se3_amd
 PT="python -u -m pytest -x -v -s --timeout 300 --timeout-method thread"
+# the bench step records the line with every side measurement (CPU baseline, configs[1] / IFT / configs[4] figures),
+# which bench.py runs only with --full; the quick, moving and mprof steps record plain lines
+BENCH_ARGS="--full $BENCH_ARGS"
 for step in "$@"; do
   echo "[gpu_call] $step $(date +%T)"
   case $step in

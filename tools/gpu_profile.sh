@@ -11,7 +11,7 @@ TAG=${TAG:-r02_prof}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 CMD="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra"
-timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err &&
+timeout -k 10 300 python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra > $OUT/trace.log 2>&1 &&
 timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE -d $OUT/f -o run --output-format csv -- $CMD > $OUT/f.log 2>&1 &&
 timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE -d $OUT/w -o run --output-format csv -- $CMD > $OUT/w.log 2>&1 &&
