@@ -9,6 +9,7 @@
  *   lafse3_objective      replaces run_quad.objective         quad_policy.py:67-91
  *   lafse3_sol_gradient   replaces run_quad.sol_gradient      quad_policy.py:94-112
  *   lafse3_get_input      replaces run_quad.get_input         quad_policy.py:202-211
+ *   lafse3_ocp_sensitivity  ocSolver + dx, du / d(p_tra, a_tra, t)  (the PDP auxiliary system, quad_OC.py:214-306)
  *
  * Every array argument is a DEVICE pointer (HBM; e.g. a torch.cuda tensor's data_ptr()), owned by
  * the caller, row-major, contiguous.  B is the batch size.  N is params.horizon (<= LAFSE3_MAX_N).
@@ -120,6 +121,24 @@ int lafse3_ocp_solve(lafse3_ctx *ctx, int64_t B, const double *ini_state, const 
                      const double *p_tra, const double *a_tra, const double *t, const double *u_last,
                      double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
                      void *stream);
+
+/* lafse3_ocp_solve plus the analytic sensitivities of its solution to theta = (p_tra[0..2], a_tra[0..2], t), the
+ * derivative the reference sketched as the PDP auxiliary system (quad_OC.py:214-306, commented out there).  The
+ * first 14 arguments and the outputs x .. iters are lafse3_ocp_solve's, bit for bit.  Then, each nullable:
+ *   dx B x 7 x (N+1) x 13 = dx_k / dtheta_q, du B x 7 x N x 4 = du_k / dtheta_q, parameter order along the axis of
+ *   7 as above; sens_status B (int32): 0 ok, 1 the solve ended with status > 1, 2 the factorisation at the optimum
+ *   met a wrong inertia -- after 1 and 2 that instance's dx and du are zero.  With dx == du == NULL the call is
+ *   lafse3_ocp_solve (sens_status is then not written).
+ * One Newton-system factorisation at the optimum z* (final mu and bound duals, delta_w = 0) and one refinement sweep
+ * per parameter, on the wave that solved the instance (implicit function theorem; grad_mode 1 of
+ * lafse3_sol_gradient uses the same sweeps for its six reward probes).  t is used as given; u_last is accepted and,
+ * like ini_state and goal, treated as a constant, so dx at stage 0 is zero.  The derivative is that of the barrier
+ * problem at the final mu: across an active-set change it is a one-sided smoothing, not a subgradient.  A solver
+ * launch for lafse3_reserve, lafse3_last_kernel_ms, the counters and lafse3_check_device. */
+int lafse3_ocp_sensitivity(lafse3_ctx *ctx, int64_t B, const double *ini_state, const double *goal,
+                           const double *p_tra, const double *a_tra, const double *t, const double *u_last,
+                           double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
+                           double *dx, double *du, int32_t *sens_status, void *stream);
 
 /* fp32 twin of lafse3_ocp_solve: the same arguments as float32 device buffers.  Inputs are
  * widened to fp64 and outputs rounded to fp32 on the device; the NLP itself is solved in fp64 (IPOPT's

@@ -299,7 +299,8 @@ __global__ void slots_init_kernel(double *R, int32_t *S, int64_t n)
     if (S) S[e] = lafse3::ST_DEVICE_ERR;
 }
 
-static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t sched_samples = 0)
+static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t sched_samples = 0,
+                  const lafse3::SensArgs *sens = nullptr)
 {
     if (A.n_inst == 0) return LAFSE3_OK;
     if (!A.iters_out && c->iters_rec) {
@@ -353,7 +354,9 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
         return LAFSE3_OK;
     }
     (void)hipEventRecord(c->ev0, st);
-    hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
+    // the sensitivity pass is compiled into a kernel of its own (ipm_kernel.hip ipm_kernel_sens)
+    if (sens) hipLaunchKernelGGL(lafse3::ipm_kernel_sens, dim3((unsigned)grid), dim3(64), 0, st, A, *sens);
+    else hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
     e = hipGetLastError();
     (void)hipEventRecord(c->ev1, st);
     c->timed = true;
@@ -382,6 +385,27 @@ int lafse3_ocp_solve(lafse3_ctx *c, int64_t B, const double *ini, const double *
     A.ini = ini; A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;
     A.x_out = x; A.u_out = u; A.lam_out = lam; A.cost_out = cost; A.status_out = status; A.iters_out = iters;
     return launch(c, A, (hipStream_t)stream);
+}
+
+int lafse3_ocp_sensitivity(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
+                           const double *a_tra, const double *t, const double *u_last, double *x, double *u,
+                           double *lam, double *cost, int32_t *status, int32_t *iters, double *dx, double *du,
+                           int32_t *sens_status, void *stream)
+{
+    if (!dx && !du)
+        return lafse3_ocp_solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream);
+    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
+    if (B > 0 && (!ini || !goal || !p_tra || !a_tra || !t)) return fail(LAFSE3_EINVAL, "null input");
+    if (B > 0x7fffffffLL) return fail(LAFSE3_EINVAL, "batch too large for one launch");
+    (void)hipSetDevice(c->device);
+    lafse3::KernelArgs A = blank_args();
+    A.mode = lafse3::MODE_SOLVE;
+    A.n_inst = B;
+    A.ini = ini; A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;
+    A.x_out = x; A.u_out = u; A.lam_out = lam; A.cost_out = cost; A.status_out = status; A.iters_out = iters;
+    lafse3::SensArgs Z;
+    Z.dx_out = dx; Z.du_out = du; Z.sens_out = sens_status;
+    return launch(c, A, (hipStream_t)stream, 0, &Z);
 }
 
 // ---- fp32 twin of lafse3_ocp_solve: float inputs/outputs at the boundary, fp64 arithmetic inside (IPOPT's
@@ -685,6 +709,6 @@ int lafse3_record_iters(lafse3_ctx *c, int32_t *buf, int64_t capacity)
 
 const char *lafse3_last_error(void) { return g_err.c_str(); }
 
-const char *lafse3_version(void) { return "lafse3 0.5.0 (gfx950)"; }
+const char *lafse3_version(void) { return "lafse3 0.6.0 (gfx950)"; }
 
 }  // extern "C"

@@ -156,6 +156,13 @@ struct KernelArgs {
     double *rws;                    // restoration-phase workspace, RWS_SIZE per slot
 };
 
+// second argument of ipm_kernel_sens (trajectory sensitivities, sens.inc).  Not part of KernelArgs: a larger
+// KernelArgs alone changed ipm_kernel's code (kernel-argument loads, register allocation).
+struct SensArgs {
+    double *dx_out, *du_out;        // B x 7 x (N+1) x 13, B x 7 x N x 4 (each nullable)
+    int32_t *sens_out;              // B: 0 ok, 1 the solve did not converge, 2 wrong inertia at z* (nullable)
+};
+
 struct Ctl {
     int N;
     double s;          // objective scaling
@@ -1689,6 +1696,35 @@ __device__ inline void tra_attitude(const double *a, double *St, double &trRt)
     trRt = Rt[0] + Rt[4] + Rt[8];
 }
 
+// x rows of dF/dtheta_q at stage k (1 <= k < N) for the pose parameters q < 6 (p_tra[0..2], a_tra[0..2]):
+// s d(grad_x cost_k)/dtheta_q by a central difference (h = 1e-5) of the analytic traversal gradient.  Shared by
+// ift_probes and the sensitivity pass (sens.inc).
+__device__ __attribute__((always_inline)) inline void tra_grad_fd(const Model &M, const Smem &S, const Ctl &C,
+                                                                  const double *a3, int q, int k, double *v)
+{
+    const double h = 1e-5;
+    double xk[NX], gp[NX], gm[NX];
+    load_stage(S, k, xk);
+    if (q < 3) {
+        double pp[3] = {S.ptra[0], S.ptra[1], S.ptra[2]}, pm[3] = {S.ptra[0], S.ptra[1], S.ptra[2]};
+        pp[q] += h;
+        pm[q] -= h;
+        state_cost_grad(M, S.at, S.goal, pp, S.wk[k], xk, gp);
+        state_cost_grad(M, S.at, S.goal, pm, S.wk[k], xk, gm);
+    } else {
+        Attitude ap = S.at, am = S.at;
+        double ah[3] = {a3[0], a3[1], a3[2]};
+        ah[q - 3] = a3[q - 3] + h;
+        tra_attitude(ah, ap.St, ap.trRt);
+        ah[q - 3] = a3[q - 3] - h;
+        tra_attitude(ah, am.St, am.trRt);
+        state_cost_grad(M, ap, S.goal, S.ptra, S.wk[k], xk, gp);
+        state_cost_grad(M, am, S.goal, S.ptra, S.wk[k], xk, gm);
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) v[i] = C.s * (gp[i] - gm[i]) / (2 * h);
+}
+
 // Returns 0 when the factorisation at z* met a wrong inertia (then the six probe rewards are R0 and the caller
 // marks their status ST_REG_FAIL: a zero p/a gradient from this fallback is not a true zero gradient).
 __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M, Smem &S, const Ctl &C, gdouble *ws,
@@ -1711,35 +1747,14 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
         bx[e] = S.x[e];
     }
     vm_sync();
-    const double h = 1e-5, delta = 1e-3;
+    const double delta = 1e-3;
     for (int q = 0; q < 6; ++q) {
         if (lane <= N) {
             const int k = lane;
             double v[NX];
 #pragma unroll
             for (int i = 0; i < NX; ++i) v[i] = 0.0;
-            if (ok && k >= 1 && k < N) {
-                double xk[NX], gp[NX], gm[NX];
-                load_stage(S, k, xk);
-                if (q < 3) {
-                    double pp[3] = {S.ptra[0], S.ptra[1], S.ptra[2]}, pm[3] = {S.ptra[0], S.ptra[1], S.ptra[2]};
-                    pp[q] += h;
-                    pm[q] -= h;
-                    state_cost_grad(M, S.at, S.goal, pp, S.wk[k], xk, gp);
-                    state_cost_grad(M, S.at, S.goal, pm, S.wk[k], xk, gm);
-                } else {
-                    Attitude ap = S.at, am = S.at;
-                    double ah[3] = {a3[0], a3[1], a3[2]};
-                    ah[q - 3] = a3[q - 3] + h;
-                    tra_attitude(ah, ap.St, ap.trRt);
-                    ah[q - 3] = a3[q - 3] - h;
-                    tra_attitude(ah, am.St, am.trRt);
-                    state_cost_grad(M, ap, S.goal, S.ptra, S.wk[k], xk, gp);
-                    state_cost_grad(M, am, S.goal, S.ptra, S.wk[k], xk, gm);
-                }
-#pragma unroll
-                for (int i = 0; i < NX; ++i) v[i] = C.s * (gp[i] - gm[i]) / (2 * h);
-            }
+            if (ok && k >= 1 && k < N) tra_grad_fd(M, S, C, a3, q, k, v);
 #pragma unroll
             for (int i = 0; i < NX; ++i) rq[i * SX + k] = v[i];
         }
@@ -1760,14 +1775,16 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
     return ok;
 }
 
-
+#include "sens.inc"
 
 // ------------------------------------------------------------------------------------------------
 // waves per SIMD the register allocation targets (LDS admits 2: Smem <= 20 KB)
 // One NLP instance (or one scored trajectory) on this wave, with the workspace slot ws.
 // Returns the instance's IPM iteration count (0 for trajectory scoring).
+// SENS (ipm_kernel_sens): the sensitivity pass of sens.inc follows a MODE_SOLVE instance; ipm_kernel compiles none of it.
+template <bool SENS>
 __device__ __attribute__((always_inline)) inline int run_instance(const KernelArgs &A, Smem &S, const int64_t inst,
-                                                                 gdouble *ws)
+                                                                 gdouble *ws, const SensArgs *Z = nullptr)
 {
     const int lane = lane_id();
     const lafse3_params &prm = A.prm;
@@ -2407,6 +2424,15 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
                 for (int q = 1; q <= 6; ++q) A.status_out[b * 9 + q] = pst;
         }
     }
+    if constexpr (SENS) {
+        // after every ordinary output is stored: the optimum, the final mu and the bound duals are still in LDS / ws
+        if (A.mode == MODE_SOLVE && (Z->dx_out || Z->du_out)) {
+            const int sst = sens_pass(prm, M, S, C, ws, a3, tt, status <= 1,
+                                      Z->dx_out ? Z->dx_out + inst * (int64_t)SENS_NP * (N + 1) * NX : nullptr,
+                                      Z->du_out ? Z->du_out + inst * (int64_t)SENS_NP * N * NU : nullptr);
+            if (lane == 0 && Z->sens_out) Z->sens_out[inst] = sst;
+        }
+    }
     PT_END(S, 10);
 #ifdef LAFSE3_PHASE_TIMERS
     if (A.ptime && lane < 16) A.ptime[inst * PT_COLS + lane] = S.pt[lane];
@@ -2528,6 +2554,15 @@ __device__ inline void sched_push(const KernelArgs &A, int64_t Bs, int64_t b, in
     }
 }
 
+// One LDS object for both kernels below: the noinline phases are compiled once for the module, and with a single
+// Smem its address is a constant in them (ds_read / ds_write at fixed offsets).  A second __shared__ Smem turned
+// every Smem reference of linear_solve and the other phases into flat accesses, in ipm_kernel's launches too.
+__device__ __attribute__((always_inline)) inline Smem &instance_smem()
+{
+    __shared__ Smem S;
+    return S;
+}
+
 // Persistent launch (A.persistent): one workgroup per SIMD slot, each wave takes the next instance from a
 // global queue head (a vector atomic by lane 0, broadcast through readfirstlane) until the queue is drained,
 // every wave reaching the exit test after each instance; its workspace slot is its workgroup's, so the
@@ -2537,7 +2572,7 @@ __device__ inline void sched_push(const KernelArgs &A, int64_t Bs, int64_t b, in
 // workgroup (tools/gpu_sched.py: 84 % slot occupancy at B = 4096).
 __global__ __launch_bounds__(64, 1) void ipm_kernel(KernelArgs A)
 {
-    __shared__ Smem S;
+    Smem &S = instance_smem();
     // one call site of run_instance (a second inlined copy doubles the code and its spill frame);
     // without A.persistent (trajectory scoring) workgroup b takes instance b once
     gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
@@ -2564,8 +2599,27 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel(KernelArgs A)
         typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;
         KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         __asm__ volatile("" : "+s"(Ap));
-        const int it = run_instance(*(const KernelArgs *)Ap, S, inst, ws);
+        const int it = run_instance<false>(*(const KernelArgs *)Ap, S, inst, ws);
         if (A.sched && inst < Bs) sched_push(A, Bs, inst, it);
+    }
+}
+
+// The persistent solver with the sensitivity pass compiled in (lafse3_ocp_sensitivity only): a second instantiation
+// of run_instance in a kernel of its own, so that ipm_kernel's code is what it is without the pass.  Its launches are
+// always persistent MODE_SOLVE launches without a probe queue, so the loop is the plain queue-head loop.
+__global__ __launch_bounds__(64, 1) void ipm_kernel_sens(KernelArgs A, SensArgs Z)
+{
+    Smem &S = instance_smem();
+    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
+    for (;;) {
+        unsigned long long v = 0ull;
+        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
+        const int64_t inst = bcast_i64((int64_t)v);
+        if (inst >= A.n_inst) break;
+        typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
+        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+        __asm__ volatile("" : "+s"(Ap));
+        run_instance<true>(*(const KernelArgs *)Ap, S, inst, ws, &Z);
     }
 }
 

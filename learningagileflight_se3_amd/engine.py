@@ -9,6 +9,7 @@ Reference interfaces mirrored (yanrui89/LearningAgileFlight_SE3):
   Engine.objective     run_quad.objective      quad_policy.py:67-91
   Engine.sol_gradient  run_quad.sol_gradient   quad_policy.py:94-112
   Engine.get_input     run_quad.get_input      quad_policy.py:202-211
+  Engine.ocp_sensitivity  ocSolver + dx*/dtheta, du*/dtheta (the PDP auxiliary system sketched in quad_OC.py:214-306)
 """
 from __future__ import annotations
 
@@ -216,6 +217,38 @@ class Engine:
                  _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]), _ptr(out["cost"]),
                  _ptr(out["status"]), _ptr(out["iters"]), self._stream()),
               "lafse3_ocp_solve_f32" if f32 else "lafse3_ocp_solve")
+        return {k: v for k, v in out.items() if v is not None}
+
+    def ocp_sensitivity(self, ini_state, goal, p_tra, a_tra, t, u_last=None, want=("x", "u", "dx", "du")):
+        """ocp_solve plus the analytic sensitivities of its solution (lafse3_ocp_sensitivity), one launch.
+
+        Returns ocp_solve's dict (x, u, lam, cost as named in ``want``; status, iters) and
+          dx (B, 7, N+1, 13) = dx_k / dtheta_q,  du (B, 7, N, 4) = du_k / dtheta_q,
+          theta = (p_tra[0..2], a_tra[0..2], t),
+          sens_status (B,) int32: 0 ok, 1 the solve ended with status > 1, 2 wrong inertia at the optimum
+          (dx and du of such an instance are zero).
+        The derivative is that of the barrier problem at the final mu (include/lafse3.h).  float64 only."""
+        d, f64 = self.device, torch.float64
+        ini = _dev_tensor(ini_state, (NX,), f64, d, "ini_state")
+        B = ini.shape[0]
+        goal = _dev_tensor(goal, (3,), f64, d, "goal")
+        p = _dev_tensor(p_tra, (3,), f64, d, "p_tra")
+        a = _dev_tensor(a_tra, (3,), f64, d, "a_tra")
+        tt = torch.as_tensor(t, dtype=f64).to(d).reshape(-1).expand(B).contiguous()
+        ul = _dev_tensor(u_last, (NU,), f64, d, "u_last", allow_none=True)
+        goal, p, a, ul = _same_batch(B, goal=goal, p_tra=p, a_tra=a, u_last=ul)
+        N = self.horizon
+        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,),
+                  "dx": (B, 7, N + 1, NX), "du": (B, 7, N, NU)}
+        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
+        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
+        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
+        if out["dx"] is not None or out["du"] is not None:   # without either the call is lafse3_ocp_solve
+            out["sens_status"] = torch.empty((B,), dtype=torch.int32, device=d)
+        check(self._L.lafse3_ocp_sensitivity(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
+                                             _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]), _ptr(out["cost"]),
+                                             _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["dx"]), _ptr(out["du"]),
+                                             _ptr(out.get("sens_status")), self._stream()), "lafse3_ocp_sensitivity")
         return {k: v for k, v in out.items() if v is not None}
 
     def objective(self, ini_state, goal, gate12, p_tra, a_tra, t, u_last=None):
