@@ -16,7 +16,8 @@
  * The library keeps no global mutable state: all state is in the opaque context (device workspace,
  * parameters).  Calls on one context must not overlap, and a context must be used from ONE stream at a
  * time: the workspace, scratch and counters are shared by every call on it and each call runs on the
- * caller's stream (use one context per stream); distinct contexts are independent.
+ * caller's stream (use one context per stream); distinct contexts are independent.  No entry point changes the
+ * calling thread's current HIP device: work for a context bound to another device switches to it and back.
  *
  * Return codes: 0 ok; LAFSE3_EINVAL bad argument; LAFSE3_EDEVICE HIP error (message via
  * lafse3_last_error).  Per-instance solver outcome is reported in `status` (never aborts):

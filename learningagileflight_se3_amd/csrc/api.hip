@@ -5,7 +5,8 @@
 
 #include <cstdio>
 #include <cstring>
-#include <mutex>
+#include <initializer_list>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -34,25 +35,66 @@ int fail(int code, const char *what, hipError_t e = hipSuccess)
     return code;
 }
 
+// Makes `dev` the calling thread's current HIP device for a scope and puts the caller's device (torch's) back on
+// every return path.  `err` is the result of the switch; an entry point whose switch failed returns LAFSE3_EDEVICE.
+struct DeviceGuard {
+    hipError_t err = hipSuccess;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev_) != hipSuccess) prev_ = -1;
+        if (prev_ == dev) prev_ = -1;   // already there: nothing to switch, nothing to put back
+        else err = hipSetDevice(dev);
+    }
+    ~DeviceGuard() { if (prev_ >= 0) (void)hipSetDevice(prev_); }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+
+private:
+    int prev_ = -1;
+};
+
+// Grow-only device array, freed with its owner.  Growing is hipFree then hipMalloc, and stays so: the blocking
+// hipFree synchronises the device, which is what makes growing safe while an earlier launch on another stream still
+// uses the old array (a stream-ordered free or allocation would not wait for it).  Contents are not kept.
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    ~DevBuf() { release(); }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    hipError_t ensure(int64_t n)
+    {
+        if (n <= cap_) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(&p_, (size_t)n * sizeof(T));
+        if (e == hipSuccess) cap_ = n;
+        else p_ = nullptr;
+        return e;
+    }
+    void release() { if (p_) (void)hipFree(p_); p_ = nullptr; cap_ = 0; }
+    T *data() const { return p_; }
+    int64_t capacity() const { return cap_; }
+
+private:
+    T *p_ = nullptr;
+    int64_t cap_ = 0;   // elements
+};
+
 }  // namespace
 
 struct lafse3_ctx {
     int device = 0;
     lafse3_params prm{};
-    double *ws = nullptr;
-    double *rws = nullptr;               // restoration-phase workspace (RWS_SIZE per slot)
-    int64_t ws_inst = 0;
-    double *tmp = nullptr;          // rewards9 scratch for sol_gradient
-    int64_t tmp_n = 0;
-    double *tmp32 = nullptr;        // fp64 staging of the fp32 twin (lafse3_ocp_solve_f32)
-    int64_t tmp32_n = 0;
-    unsigned long long *counters = nullptr;   // [0..2] iteration / sweep / trial totals, [3] work-queue head,
-                                              // [4] device error word (ipm_kernel.hip ERR_*: kept until
-                                              // lafse3_check_device reports it), [5..6] restoration counts;
-                                              // words N_COUNTERS.. are trajectory scoring's (lafse3_reward)
+    DevBuf<double> ws, rws;              // solver and restoration-phase workspace (WS_SIZE / RWS_SIZE per slot)
+    DevBuf<double> tmp;                  // rewards9 scratch for sol_gradient, control trajectory of get_input
+    DevBuf<double> tmp32;                // fp64 staging of the fp32 twin (lafse3_ocp_solve_f32)
+    DevBuf<unsigned long long> counters;   // [0..2] iteration / sweep / trial totals, [3] work-queue head,
+                                           // [4] device error word (ipm_kernel.hip ERR_*: kept until
+                                           // lafse3_check_device reports it), [5..6] restoration counts;
+                                           // words N_COUNTERS.. are trajectory scoring's (lafse3_reward)
     int64_t slots = 0;                         // resident solver waves: CUs x 4 SIMDs x waves per SIMD
-    unsigned *sched = nullptr;                 // sol_gradient probe queue (ipm_kernel.hip sched_next)
-    int64_t sched_n = 0;
+    DevBuf<unsigned> sched;                    // sol_gradient probe queue (ipm_kernel.hip sched_next)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     double *trace = nullptr;   // debug trace target (device), see lafse3_debug_trace
@@ -66,11 +108,40 @@ struct lafse3_ctx {
     // private stream of the context: the counters of the last solver launch are read (and its error word cleared)
     // here after ev1 has completed, never on the caller's launch stream, which the caller may have destroyed since
     hipStream_t aux = nullptr;
+
+    ~lafse3_ctx()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (aux) (void)hipStreamDestroy(aux);
+    }
 };
 
+using lafse3::N_COUNTERS;
+static_assert(N_COUNTERS > lafse3::CNT_ERR && N_COUNTERS > lafse3::CNT_RESTO + 1,
+              "N_COUNTERS must cover the error word and both restoration counts");
 static size_t ws_doubles(int64_t n) { return (size_t)n * (size_t)lafse3::WS_SIZE; }
-constexpr int N_COUNTERS = 7;   // KernelArgs::counters words
-static int ensure_sched(lafse3_ctx *c, int64_t B);
+
+// The flat one-dimensional helper launches: one thread per element of n, 256 per block.
+template <typename K, typename... Args>
+static int launch_flat(K kernel, int64_t n, hipStream_t st, const char *what, Args... args)
+{
+    const int tpb = 256;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + tpb - 1) / tpb)), dim3(tpb), 0, st, args...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? LAFSE3_OK : fail(LAFSE3_EDEVICE, what, e);
+}
+
+// Opening of the solver and scoring entry points: the context and batch, the pointers a non-empty batch needs, and
+// the one-launch limit on B x per NLP instances (the kernels index instances with 32 bits).
+static int check_call(const lafse3_ctx *c, int64_t B, std::initializer_list<const void *> required, int per = 1)
+{
+    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
+    for (const void *p : required)
+        if (B > 0 && !p) return fail(LAFSE3_EINVAL, "null argument");
+    if (B > 0x7fffffffLL / per) return fail(LAFSE3_EINVAL, "batch too large for one launch");
+    return LAFSE3_OK;
+}
 
 extern "C" {
 
@@ -106,25 +177,19 @@ int lafse3_stream_create(int device, void **stream)
 {
     if (!stream) return fail(LAFSE3_EINVAL, "null stream");
     *stream = nullptr;
-    if (device < 0) {
-        const hipError_t e = hipGetDevice(&device);
-        if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipGetDevice", e);
-    }
-    int cus = 0, prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    hipError_t e = hipSetDevice(device);
+    hipError_t e;
+    if (device < 0 && (e = hipGetDevice(&device)) != hipSuccess) return fail(LAFSE3_EDEVICE, "hipGetDevice", e);
+    DeviceGuard dev(device);
+    int cus = 0;
+    e = dev.err;
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e != hipSuccess || cus <= 0) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return fail(LAFSE3_EDEVICE, "CU count", e);
-    }
+    if (e != hipSuccess || cus <= 0) return fail(LAFSE3_EDEVICE, "CU count", e);
     // a CU-masked stream gets a hardware queue of its own (the runtime does not share masked queues); the mask
     // enables every CU, so the stream runs exactly as an ordinary one otherwise
     std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0xffffffffu);
     if (cus % 32) mask.back() = (1u << (cus % 32)) - 1u;
     hipStream_t st = nullptr;
     e = hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data());
-    if (prev >= 0) (void)hipSetDevice(prev);   // the caller's current device (torch's) stays as it was
     if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipExtStreamCreateWithCUMask", e);
     *stream = (void *)st;
     return LAFSE3_OK;
@@ -141,66 +206,41 @@ int lafse3_stream_destroy(void *stream)
 int lafse3_create(lafse3_ctx **ctx, int device)
 {
     if (!ctx) return fail(LAFSE3_EINVAL, "null ctx");
-    lafse3_ctx *c = new lafse3_ctx();
     hipError_t e;
-    if (device < 0) {
-        e = hipGetDevice(&c->device);
-        if (e != hipSuccess) { delete c; return fail(LAFSE3_EDEVICE, "hipGetDevice", e); }
-    } else {
-        c->device = device;
-    }
-    e = hipSetDevice(c->device);
-    if (e != hipSuccess) { delete c; return fail(LAFSE3_EDEVICE, "hipSetDevice", e); }
+    if (device < 0 && (e = hipGetDevice(&device)) != hipSuccess) return fail(LAFSE3_EDEVICE, "hipGetDevice", e);
+    DeviceGuard dev(device);   // declared before c: a context abandoned below is destroyed on its own device
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
+    std::unique_ptr<lafse3_ctx> c(new lafse3_ctx());
+    c->device = device;
     lafse3_default_params(&c->prm);
-    e = hipMalloc(&c->counters, 2 * N_COUNTERS * sizeof(unsigned long long));
-    if (e != hipSuccess) { delete c; return fail(LAFSE3_EDEVICE, "hipMalloc counters", e); }
+    e = c->counters.ensure(2 * N_COUNTERS);
+    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc counters", e);
     {
         // zeroed on a private stream and waited for there (a device-wide synchronize would also wait for other
         // contexts' solver launches in flight); complete before this call returns, so before any launch on it
         hipStream_t zs = nullptr;
         e = hipStreamCreateWithFlags(&zs, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMemsetAsync(c->counters, 0, 2 * N_COUNTERS * sizeof(unsigned long long), zs);
+        if (e == hipSuccess)
+            e = hipMemsetAsync(c->counters.data(), 0, 2 * N_COUNTERS * sizeof(unsigned long long), zs);
         if (e == hipSuccess) e = hipStreamSynchronize(zs);
         if (zs) (void)hipStreamDestroy(zs);
     }
-    if (e != hipSuccess) {
-        (void)hipFree(c->counters);
-        delete c;
-        return fail(LAFSE3_EDEVICE, "hipMemset counters", e);
-    }
+    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMemset counters", e);
     int cus = 0;
     e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-    if (e != hipSuccess || cus <= 0) {
-        (void)hipFree(c->counters);
-        delete c;
-        return fail(LAFSE3_EDEVICE, "hipDeviceGetAttribute(CU count)", e);
-    }
+    if (e != hipSuccess || cus <= 0) return fail(LAFSE3_EDEVICE, "hipDeviceGetAttribute(CU count)", e);
     c->slots = (int64_t)cus * 4;   // one wave per SIMD (ipm_kernel __launch_bounds__(64, 1))
     if ((e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking)) != hipSuccess) {
-        if (c->ev0) (void)hipEventDestroy(c->ev0);
-        if (c->ev1) (void)hipEventDestroy(c->ev1);
-        (void)hipFree(c->counters);
-        delete c;
+        (e = hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking)) != hipSuccess)
         return fail(LAFSE3_EDEVICE, "hipEventCreate / hipStreamCreate", e);
-    }
-    *ctx = c;
+    *ctx = c.release();
     return LAFSE3_OK;
 }
 
 int lafse3_destroy(lafse3_ctx *c)
 {
     if (!c) return LAFSE3_OK;
-    (void)hipSetDevice(c->device);
-    if (c->ws) (void)hipFree(c->ws);
-    if (c->rws) (void)hipFree(c->rws);
-    if (c->tmp) (void)hipFree(c->tmp);
-    if (c->counters) (void)hipFree(c->counters);
-    if (c->tmp32) (void)hipFree(c->tmp32);
-    if (c->sched) (void)hipFree(c->sched);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->aux) (void)hipStreamDestroy(c->aux);
+    DeviceGuard dev(c->device);
     delete c;
     return LAFSE3_OK;
 }
@@ -237,56 +277,34 @@ int lafse3_get_params(const lafse3_ctx *c, lafse3_params *p)
     return LAFSE3_OK;
 }
 
-int lafse3_reserve(lafse3_ctx *c, int64_t n)
-{
-    if (!c || n < 0) return fail(LAFSE3_EINVAL, "bad reserve");
-    if (n > 0) {   // the probe queue of a sol_gradient launch of up to n samples (n instances cover n / 9)
-        const int rq = ensure_sched(c, n);
-        if (rq) return rq;
-    }
-    if (n > c->slots) n = c->slots;   // persistent solver: one workspace slot per resident wave
-    if (n <= c->ws_inst) return LAFSE3_OK;
-    (void)hipSetDevice(c->device);
-    if (c->ws) { (void)hipFree(c->ws); c->ws = nullptr; c->ws_inst = 0; }
-    if (c->rws) { (void)hipFree(c->rws); c->rws = nullptr; }
-    hipError_t e = hipMalloc(&c->ws, ws_doubles(n) * sizeof(double));
-    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc workspace", e);
-    e = hipMalloc(&c->rws, (size_t)n * lafse3::RWS_SIZE * sizeof(double));
-    if (e != hipSuccess) {
-        (void)hipFree(c->ws);
-        c->ws = nullptr;
-        return fail(LAFSE3_EDEVICE, "hipMalloc restoration workspace", e);
-    }
-    c->ws_inst = n;
-    return LAFSE3_OK;
-}
-
-static int ensure_tmp(lafse3_ctx *c, int64_t n)
-{
-    if (n <= c->tmp_n) return LAFSE3_OK;
-    if (c->tmp) (void)hipFree(c->tmp);
-    c->tmp = nullptr;
-    c->tmp_n = 0;
-    hipError_t e = hipMalloc(&c->tmp, (size_t)n * sizeof(double));
-    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc scratch", e);
-    c->tmp_n = n;
-    return LAFSE3_OK;
-}
-
 // probe queue of a sol_gradient launch of B samples: 2 NB + 1 counters + NB x B bucket slots
 static int64_t sched_words(int64_t B) { return 2 * lafse3::SCHED_NB + 1 + lafse3::SCHED_NB * B; }
 
-static int ensure_sched(lafse3_ctx *c, int64_t B)
+// workspace slots of n resident waves: ws and rws grow together, and a failed allocation leaves both empty
+static int reserve_ws(lafse3_ctx *c, int64_t n)
 {
-    const int64_t n = sched_words(B);
-    if (n <= c->sched_n) return LAFSE3_OK;
-    if (c->sched) (void)hipFree(c->sched);
-    c->sched = nullptr;
-    c->sched_n = 0;
-    hipError_t e = hipMalloc(&c->sched, (size_t)n * sizeof(unsigned));
-    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc probe queue", e);
-    c->sched_n = n;
-    return LAFSE3_OK;
+    const char *what = "hipMalloc workspace";
+    hipError_t e = c->ws.ensure((int64_t)ws_doubles(n));
+    if (e == hipSuccess) {
+        what = "hipMalloc restoration workspace";
+        e = c->rws.ensure(n * lafse3::RWS_SIZE);
+    }
+    if (e == hipSuccess) return LAFSE3_OK;
+    c->ws.release();
+    c->rws.release();
+    return fail(LAFSE3_EDEVICE, what, e);
+}
+
+int lafse3_reserve(lafse3_ctx *c, int64_t n)
+{
+    if (!c || n < 0) return fail(LAFSE3_EINVAL, "bad reserve");
+    DeviceGuard dev(c->device);
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
+    if (n > 0) {   // the probe queue of a sol_gradient launch of up to n samples (n instances cover n / 9)
+        const hipError_t e = c->sched.ensure(sched_words(n));
+        if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc probe queue", e);
+    }
+    return reserve_ws(c, n < c->slots ? n : c->slots);   // persistent solver: one workspace slot per resident wave
 }
 
 // rewards9 / status9 slots before a sol_gradient launch: NaN / ST_DEVICE_ERR, overwritten by every solve that
@@ -303,7 +321,10 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
                   const lafse3::SensArgs *sens = nullptr)
 {
     if (A.n_inst == 0) return LAFSE3_OK;
-    if (!A.iters_out && c->iters_rec) {
+    // trajectory scoring (MODE_REWARD) counts nothing and has its own queue head: it leaves the last solver
+    // launch's counters, error word, timing events and stream alone, and records no iteration counts
+    const bool scoring = A.mode == lafse3::MODE_REWARD;
+    if (!A.iters_out && c->iters_rec && !scoring) {
         // slots the kernel writes: b * 9 + j for sol_gradient (both gradient modes), the instance index otherwise
         const int64_t need = (A.mode == lafse3::MODE_GRAD) ? sched_samples * 9 : A.n_inst;
         if (need > c->iters_cap) {
@@ -316,16 +337,13 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
     }
     // persistent grid: one workgroup per SIMD slot (fewer when the batch is smaller), workspace per workgroup
     const int64_t grid = A.n_inst < c->slots ? A.n_inst : c->slots;
-    int rc = lafse3_reserve(c, grid);
+    const int rc = reserve_ws(c, grid);
     if (rc) return rc;
     A.persistent = 1;
     A.prm = c->prm;
-    A.ws = c->ws;
-    A.rws = c->rws;
-    // trajectory scoring (MODE_REWARD) counts nothing and has its own queue head: it leaves the last solver
-    // launch's counters, error word, timing events and stream alone
-    const bool scoring = A.mode == lafse3::MODE_REWARD;
-    A.counters = scoring ? c->counters + N_COUNTERS : c->counters;
+    A.ws = c->ws.data();
+    A.rws = c->rws.data();
+    A.counters = c->counters.data() + (scoring ? N_COUNTERS : 0);
     A.trace = c->trace;
     A.trace_iters = c->trace_iters;
     A.ptime = c->ptime;
@@ -341,11 +359,11 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
     if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMemsetAsync", e);
     A.sched = nullptr;
     if (sched_samples > 0) {
-        rc = ensure_sched(c, sched_samples);
-        if (rc) return rc;
-        e = hipMemsetAsync(c->sched, 0, (size_t)sched_words(sched_samples) * sizeof(unsigned), st);
+        e = c->sched.ensure(sched_words(sched_samples));
+        if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc probe queue", e);
+        e = hipMemsetAsync(c->sched.data(), 0, (size_t)sched_words(sched_samples) * sizeof(unsigned), st);
         if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMemsetAsync probe queue", e);
-        A.sched = c->sched;
+        A.sched = c->sched.data();
     }
     if (scoring) {
         hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
@@ -371,20 +389,28 @@ static lafse3::KernelArgs blank_args()
     return A;
 }
 
-int lafse3_ocp_solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
-                     const double *a_tra, const double *t, const double *u_last, double *x, double *u, double *lam,
-                     double *cost, int32_t *status, int32_t *iters, void *stream)
+// lafse3_ocp_solve and, with sens, lafse3_ocp_sensitivity: the one place that fills the MODE_SOLVE arguments
+static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
+                 const double *a_tra, const double *t, const double *u_last, double *x, double *u, double *lam,
+                 double *cost, int32_t *status, int32_t *iters, void *stream, const lafse3::SensArgs *sens)
 {
-    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
-    if (B > 0 && (!ini || !goal || !p_tra || !a_tra || !t)) return fail(LAFSE3_EINVAL, "null input");
-    if (B > 0x7fffffffLL) return fail(LAFSE3_EINVAL, "batch too large for one launch");
-    (void)hipSetDevice(c->device);
+    if (const int rc = check_call(c, B, {ini, goal, p_tra, a_tra, t})) return rc;
+    if (B == 0) return LAFSE3_OK;
+    DeviceGuard dev(c->device);
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
     lafse3::KernelArgs A = blank_args();
     A.mode = lafse3::MODE_SOLVE;
     A.n_inst = B;
     A.ini = ini; A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;
     A.x_out = x; A.u_out = u; A.lam_out = lam; A.cost_out = cost; A.status_out = status; A.iters_out = iters;
-    return launch(c, A, (hipStream_t)stream);
+    return launch(c, A, (hipStream_t)stream, 0, sens);
+}
+
+int lafse3_ocp_solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
+                     const double *a_tra, const double *t, const double *u_last, double *x, double *u, double *lam,
+                     double *cost, int32_t *status, int32_t *iters, void *stream)
+{
+    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr);
 }
 
 int lafse3_ocp_sensitivity(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
@@ -392,20 +418,11 @@ int lafse3_ocp_sensitivity(lafse3_ctx *c, int64_t B, const double *ini, const do
                            double *lam, double *cost, int32_t *status, int32_t *iters, double *dx, double *du,
                            int32_t *sens_status, void *stream)
 {
-    if (!dx && !du)
-        return lafse3_ocp_solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream);
-    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
-    if (B > 0 && (!ini || !goal || !p_tra || !a_tra || !t)) return fail(LAFSE3_EINVAL, "null input");
-    if (B > 0x7fffffffLL) return fail(LAFSE3_EINVAL, "batch too large for one launch");
-    (void)hipSetDevice(c->device);
-    lafse3::KernelArgs A = blank_args();
-    A.mode = lafse3::MODE_SOLVE;
-    A.n_inst = B;
-    A.ini = ini; A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;
-    A.x_out = x; A.u_out = u; A.lam_out = lam; A.cost_out = cost; A.status_out = status; A.iters_out = iters;
     lafse3::SensArgs Z;
     Z.dx_out = dx; Z.du_out = du; Z.sens_out = sens_status;
-    return launch(c, A, (hipStream_t)stream, 0, &Z);
+    // without dx and du the call is lafse3_ocp_solve
+    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream,
+                 dx || du ? &Z : nullptr);
 }
 
 // ---- fp32 twin of lafse3_ocp_solve: float inputs/outputs at the boundary, fp64 arithmetic inside (IPOPT's
@@ -425,36 +442,26 @@ __global__ void f64_to_f32_kernel(const double *in, float *out, int64_t n)
 static int convert(const void *in, void *out, int64_t n, bool to64, hipStream_t st)
 {
     if (n == 0 || !in || !out) return LAFSE3_OK;
-    const int tpb = 256;
-    const unsigned g = (unsigned)((n + tpb - 1) / tpb);
-    if (to64) hipLaunchKernelGGL(f32_to_f64_kernel, dim3(g), dim3(tpb), 0, st, (const float *)in, (double *)out, n);
-    else hipLaunchKernelGGL(f64_to_f32_kernel, dim3(g), dim3(tpb), 0, st, (const double *)in, (float *)out, n);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LAFSE3_OK : fail(LAFSE3_EDEVICE, "fp32/fp64 conversion launch", e);
+    const char *what = "fp32/fp64 conversion launch";
+    if (to64) return launch_flat(f32_to_f64_kernel, n, st, what, (const float *)in, (double *)out, n);
+    return launch_flat(f64_to_f32_kernel, n, st, what, (const double *)in, (float *)out, n);
 }
 
 int lafse3_ocp_solve_f32(lafse3_ctx *c, int64_t B, const float *ini, const float *goal, const float *p_tra,
                          const float *a_tra, const float *t, const float *u_last, float *x, float *u, float *lam,
                          float *cost, int32_t *status, int32_t *iters, void *stream)
 {
-    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
-    if (B > 0 && (!ini || !goal || !p_tra || !a_tra || !t)) return fail(LAFSE3_EINVAL, "null input");
-    if (B > 0x7fffffffLL) return fail(LAFSE3_EINVAL, "batch too large for one launch");
+    if (const int rc = check_call(c, B, {ini, goal, p_tra, a_tra, t})) return rc;
     if (B == 0) return LAFSE3_OK;
-    (void)hipSetDevice(c->device);
+    DeviceGuard dev(c->device);
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
     const int64_t N = c->prm.horizon;
     const int64_t nin = B * (13 + 3 + 3 + 3 + 1 + 4);
     const int64_t nx = x ? B * (N + 1) * 13 : 0, nu = u ? B * N * 4 : 0, nl = lam ? B * N * 13 : 0, nc = cost ? B : 0;
     const int64_t need = nin + nx + nu + nl + nc;
-    if (need > c->tmp32_n) {
-        if (c->tmp32) (void)hipFree(c->tmp32);
-        c->tmp32 = nullptr;
-        c->tmp32_n = 0;
-        hipError_t e = hipMalloc(&c->tmp32, (size_t)need * sizeof(double));
-        if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc fp32 staging", e);
-        c->tmp32_n = need;
-    }
-    double *d = c->tmp32;
+    const hipError_t e = c->tmp32.ensure(need);
+    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc fp32 staging", e);
+    double *d = c->tmp32.data();
     double *dini = d, *dgoal = dini + 13 * B, *dp = dgoal + 3 * B, *da = dp + 3 * B, *dt = da + 3 * B, *dul = dt + B;
     double *dx = dul + 4 * B, *du = dx + nx, *dl = du + nu, *dc = dl + nl;
     hipStream_t st = (hipStream_t)stream;
@@ -476,10 +483,10 @@ int lafse3_objective(lafse3_ctx *c, int64_t B, const double *ini, const double *
                      const double *p_tra, const double *a_tra, const double *t, const double *u_last, double *reward,
                      int32_t *status, void *stream)
 {
-    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
-    if (B > 0 && (!ini || !goal || !gate12 || !p_tra || !a_tra || !t || !reward))
-        return fail(LAFSE3_EINVAL, "null argument");
-    (void)hipSetDevice(c->device);
+    if (const int rc = check_call(c, B, {ini, goal, gate12, p_tra, a_tra, t, reward})) return rc;
+    if (B == 0) return LAFSE3_OK;
+    DeviceGuard dev(c->device);
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
     lafse3::KernelArgs A = blank_args();
     A.mode = lafse3::MODE_OBJECTIVE;
     A.n_inst = B;
@@ -492,18 +499,17 @@ int lafse3_sol_gradient(lafse3_ctx *c, int64_t B, const double *ini, const doubl
                         const float *dnn_out, const double *u_last, double *out8, double *rewards9, int32_t *status9,
                         void *stream)
 {
-    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
-    if (B > 0 && (!ini || !goal || !gate12 || !dnn_out || !out8)) return fail(LAFSE3_EINVAL, "null argument");
-    if (B * 9 > 0x7fffffffLL) return fail(LAFSE3_EINVAL, "batch too large for one launch");
-    const bool ift = c && c->prm.grad_mode == 1;
+    if (const int rc = check_call(c, B, {ini, goal, gate12, dnn_out, out8}, 9)) return rc;
+    const bool ift = c->prm.grad_mode == 1;
     if (ift && u_last) return fail(LAFSE3_EINVAL, "grad_mode 1 (IFT) linearises the nominal solve: u_last must be NULL");
     if (B == 0) return LAFSE3_OK;
-    (void)hipSetDevice(c->device);
+    DeviceGuard dev(c->device);
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
     double *R = rewards9;
     if (!R) {
-        int rc = ensure_tmp(c, B * 9);
-        if (rc) return rc;
-        R = c->tmp;
+        const hipError_t e = c->tmp.ensure(B * 9);
+        if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc scratch", e);
+        R = c->tmp.data();
     }
     lafse3::KernelArgs A = blank_args();
     A.mode = lafse3::MODE_GRAD;
@@ -511,44 +517,34 @@ int lafse3_sol_gradient(lafse3_ctx *c, int64_t B, const double *ini, const doubl
     A.ini = ini; A.goal = goal; A.gate12 = gate12; A.dnn = dnn_out; A.ulast = u_last;
     A.reward_out = R; A.status_out = status9;
     hipStream_t st = (hipStream_t)stream;
-    {
-        const int tpb = 256;
-        hipLaunchKernelGGL(slots_init_kernel, dim3((unsigned)((9 * B + tpb - 1) / tpb)), dim3(tpb), 0, st, R, status9,
-                           9 * B);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "slots_init_kernel launch", e);
-    }
-    int rc = launch(c, A, st, B);   // nominal solves first, then the probes longest-first (sched_next)
+    int rc = launch_flat(slots_init_kernel, 9 * B, st, "slots_init_kernel launch", R, status9, 9 * B);
     if (rc) return rc;
-    const int tpb = 256;
-    hipLaunchKernelGGL(lafse3::assemble_kernel, dim3((unsigned)((B + tpb - 1) / tpb)), dim3(tpb), 0, st, B, R,
-                       dnn_out, out8);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "assemble_kernel launch", e);
-    return LAFSE3_OK;
+    rc = launch(c, A, st, B);   // nominal solves first, then the probes longest-first (sched_next)
+    if (rc) return rc;
+    return launch_flat(lafse3::assemble_kernel, B, st, "assemble_kernel launch", B, R, dnn_out, out8);
 }
 
 int lafse3_get_input(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *u_last,
                      const float *dnn_out, double *u0, double *x, int32_t *status, void *stream)
 {
-    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
-    if (B > 0 && (!ini || !goal || !dnn_out || !u0)) return fail(LAFSE3_EINVAL, "null argument");
+    if (const int rc = check_call(c, B, {ini, goal, dnn_out, u0})) return rc;
     if (B == 0) return LAFSE3_OK;
-    (void)hipSetDevice(c->device);
+    DeviceGuard dev(c->device);
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
     const int N = c->prm.horizon;
     // full control trajectory goes to scratch; u0 is its first row (copied with a 2-D memcpy)
-    int rc = ensure_tmp(c, B * (int64_t)N * 4);
-    if (rc) return rc;
+    hipError_t e = c->tmp.ensure(B * (int64_t)N * 4);
+    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMalloc scratch", e);
     lafse3::KernelArgs A = blank_args();
     A.mode = lafse3::MODE_GETINPUT;
     A.n_inst = B;
     A.ini = ini; A.goal = goal; A.dnn = dnn_out; A.ulast = u_last;
-    A.u_out = c->tmp; A.x_out = x; A.status_out = status;
+    A.u_out = c->tmp.data(); A.x_out = x; A.status_out = status;
     hipStream_t st = (hipStream_t)stream;
-    rc = launch(c, A, st);
+    const int rc = launch(c, A, st);
     if (rc) return rc;
-    hipError_t e = hipMemcpy2DAsync(u0, 4 * sizeof(double), c->tmp, (size_t)N * 4 * sizeof(double),
-                                    4 * sizeof(double), (size_t)B, hipMemcpyDeviceToDevice, st);
+    e = hipMemcpy2DAsync(u0, 4 * sizeof(double), c->tmp.data(), (size_t)N * 4 * sizeof(double), 4 * sizeof(double),
+                         (size_t)B, hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMemcpy2DAsync", e);
     return LAFSE3_OK;
 }
@@ -556,32 +552,27 @@ int lafse3_get_input(lafse3_ctx *c, int64_t B, const double *ini, const double *
 int lafse3_reward(lafse3_ctx *c, int64_t B, const double *x, const double *goal, const double *gate12, double *reward,
                   void *stream)
 {
-    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
-    if (B > 0 && (!x || !goal || !gate12 || !reward)) return fail(LAFSE3_EINVAL, "null argument");
-    if (B > 0x7fffffffLL) return fail(LAFSE3_EINVAL, "batch too large for one launch");
+    if (const int rc = check_call(c, B, {x, goal, gate12, reward})) return rc;
     if (B == 0) return LAFSE3_OK;
-    (void)hipSetDevice(c->device);
+    DeviceGuard dev(c->device);
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
     lafse3::KernelArgs A = blank_args();
     A.mode = lafse3::MODE_REWARD;
     A.n_inst = B;
     A.x_in = x; A.goal = goal; A.gate12 = gate12; A.reward_out = reward;
     // the same persistent launch as the solves: min(B, slots) workgroups, each with its own workspace slot
-    const int32_t *keep = c->iters_rec;   // trajectory scoring records no iteration counts
-    c->iters_rec = nullptr;
-    const int rc = launch(c, A, (hipStream_t)stream);
-    c->iters_rec = const_cast<int32_t *>(keep);
-    return rc;
+    return launch(c, A, (hipStream_t)stream);
 }
 
 int lafse3_traversal_time(lafse3_ctx *c, int64_t B, const double *state, const double *final_point,
                           const double *gate12, const double *velo, double w, const float *dnn2_weights,
                           double *t_out, int32_t *iters, void *stream)
 {
-    if (!c || B < 0) return fail(LAFSE3_EINVAL, "bad ctx / batch");
-    if (B > 0 && (!state || !final_point || !gate12 || !velo || !dnn2_weights || !t_out))
-        return fail(LAFSE3_EINVAL, "null argument");
+    if (const int rc = check_call(c, B, {state, final_point, gate12, velo, dnn2_weights, t_out})) return rc;
     if (B == 0) return LAFSE3_OK;
-    (void)hipSetDevice(c->device);
+    if (((uintptr_t)dnn2_weights & 15) != 0) return fail(LAFSE3_EINVAL, "dnn2_weights not 16-byte aligned");
+    DeviceGuard dev(c->device);
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
     lafse3::TTArgs A;
     A.B = B;
     A.state = state; A.final_point = final_point; A.gate = gate12; A.velo = velo;
@@ -589,7 +580,6 @@ int lafse3_traversal_time(lafse3_ctx *c, int64_t B, const double *state, const d
     A.weights = dnn2_weights;
     A.t_out = t_out;
     A.iters = iters;
-    if (((uintptr_t)dnn2_weights & 15) != 0) return fail(LAFSE3_EINVAL, "dnn2_weights not 16-byte aligned");
     // one wave per episode, grid-stride: two rounds of resident waves (1 per SIMD at its register count)
     const int64_t grid = B < 2 * c->slots ? B : 2 * c->slots;
     hipLaunchKernelGGL(lafse3::traversal_time_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, A);
@@ -609,15 +599,22 @@ float lafse3_last_kernel_ms(const lafse3_ctx *c)
     return ms;
 }
 
-static int read_counters(lafse3_ctx *c, unsigned long long h[N_COUNTERS])
+// The three counter readers open alike: arguments, then a context with no solver launch yet (which
+// lafse3_check_device passes as clean, idle_ok, and the other two refuse), then the read into h.  LAFSE3_EINVAL
+// means that nothing was read.
+static int read_counters(lafse3_ctx *c, const void *out, bool idle_ok, unsigned long long (&h)[N_COUNTERS])
 {
+    if (!c || !out) return fail(LAFSE3_EINVAL, "null argument");
+    if (!c->timed) return idle_ok ? LAFSE3_OK : fail(LAFSE3_EINVAL, "no solver launch on this context yet");
     // the counters are written by the last solver launch: wait for its end event (recorded on the launch stream,
     // which may be a non-blocking torch stream or one the caller has destroyed since), then copy on the context's
     // own stream -- not on the launch stream and not on the legacy default stream
-    (void)hipSetDevice(c->device);
-    hipError_t e = hipEventSynchronize(c->ev1);
+    DeviceGuard dev(c->device);
+    hipError_t e = dev.err;
+    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", e);
+    e = hipEventSynchronize(c->ev1);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(h, c->counters, N_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->aux);
+        e = hipMemcpyAsync(h, c->counters.data(), sizeof(h), hipMemcpyDeviceToHost, c->aux);
     if (e == hipSuccess) e = hipStreamSynchronize(c->aux);
     if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMemcpyAsync counters", e);
     if (h[lafse3::CNT_ERR]) {
@@ -633,20 +630,18 @@ static int read_counters(lafse3_ctx *c, unsigned long long h[N_COUNTERS])
 
 int lafse3_last_counters(lafse3_ctx *c, int64_t counters[3])
 {
-    if (!c || !counters) return fail(LAFSE3_EINVAL, "null argument");
     unsigned long long h[N_COUNTERS] = {};
-    if (!c->timed) return fail(LAFSE3_EINVAL, "no solver launch on this context yet");
-    const int rc = read_counters(c, h);
+    const int rc = read_counters(c, counters, false, h);
+    if (rc == LAFSE3_EINVAL) return rc;
     for (int i = 0; i < 3; ++i) counters[i] = (int64_t)h[i];
     return rc;
 }
 
 int lafse3_last_resto_counters(lafse3_ctx *c, int64_t counters[2])
 {
-    if (!c || !counters) return fail(LAFSE3_EINVAL, "null argument");
     unsigned long long h[N_COUNTERS] = {};
-    if (!c->timed) return fail(LAFSE3_EINVAL, "no solver launch on this context yet");
-    const int rc = read_counters(c, h);
+    const int rc = read_counters(c, counters, false, h);
+    if (rc == LAFSE3_EINVAL) return rc;
     counters[0] = (int64_t)h[lafse3::CNT_RESTO];
     counters[1] = (int64_t)h[lafse3::CNT_RESTO + 1];
     return rc;
@@ -654,16 +649,16 @@ int lafse3_last_resto_counters(lafse3_ctx *c, int64_t counters[2])
 
 int lafse3_check_device(lafse3_ctx *c)
 {
-    if (!c) return fail(LAFSE3_EINVAL, "null ctx");
-    if (!c->timed) return LAFSE3_OK;
     unsigned long long h[N_COUNTERS] = {};
-    const int rc = read_counters(c, h);
-    if (rc != LAFSE3_OK && !h[lafse3::CNT_ERR]) return rc;   // the copy itself failed
-    if (h[lafse3::CNT_ERR]) {   // reported: clear it for the launches that follow
-        hipError_t e = hipMemsetAsync(c->counters + lafse3::CNT_ERR, 0, sizeof(unsigned long long), c->aux);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->aux);
-        if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMemsetAsync error word", e);
-    }
+    const int rc = read_counters(c, c, true, h);
+    if (!h[lafse3::CNT_ERR]) return rc;   // clean, nothing to read yet, or the read itself failed
+    // reported: clear it for the launches that follow
+    DeviceGuard dev(c->device);
+    hipError_t e = dev.err;
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->counters.data() + lafse3::CNT_ERR, 0, sizeof(unsigned long long), c->aux);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->aux);
+    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMemsetAsync error word", e);
     return rc;
 }
 

@@ -48,6 +48,7 @@ enum { ST_SOLVED = 0, ST_ACCEPTABLE = 1, ST_MAXITER = 2, ST_LS_FAIL = 3, ST_NONF
 // device error word (KernelArgs::counters[CNT_ERR], read back by lafse3_last_counters / lafse3_check_device)
 constexpr int CNT_ERR = 4;
 constexpr int CNT_RESTO = 5;   // [5] restoration-phase entries, [6] successful returns (summed over instances)
+constexpr int N_COUNTERS = 7;  // KernelArgs::counters words of one launch (the host zeroes and reads back this many)
 enum : unsigned long long { ERR_PROBE_LOST = 1ull };
 
 // per-instance HBM workspace (doubles)

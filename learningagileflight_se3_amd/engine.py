@@ -13,6 +13,7 @@ Reference interfaces mirrored (yanrui89/LearningAgileFlight_SE3):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -48,6 +49,52 @@ def _same_batch(B, **named):
                 raise ValueError(f"{name}: batch {v.shape[0]} != {B} (the batch of ini_state)")
         out.append(v)
     return out
+
+
+def _solve_inputs(device, dtype, ini_state, goal, p_tra, a_tra, t, u_last=None, gate12=None, with_gate=False):
+    """The solve inputs as ``dtype`` tensors on ``device`` with the batch B of ini_state (a scalar ``t`` expands
+    to (B,), a one-row ``u_last`` to B rows): (B, ini, goal, p_tra, a_tra, t, u_last, gate12), gate12 None unless
+    ``with_gate``.  A wrong trailing shape or batch raises ValueError naming the argument."""
+    ini = _dev_tensor(ini_state, (NX,), dtype, device, "ini_state")
+    B = ini.shape[0]
+    named = {"goal": _dev_tensor(goal, (3,), dtype, device, "goal"),
+             "p_tra": _dev_tensor(p_tra, (3,), dtype, device, "p_tra"),
+             "a_tra": _dev_tensor(a_tra, (3,), dtype, device, "a_tra"),
+             "u_last": _dev_tensor(u_last, (NU,), dtype, device, "u_last", allow_none=True),
+             "gate12": _dev_tensor(gate12, (12,), dtype, device, "gate12") if with_gate else None}
+    tt = torch.as_tensor(t, dtype=dtype).to(device).reshape(-1).expand(B).contiguous()
+    goal, p, a, ul, g12 = _same_batch(B, **named)
+    return B, ini, goal, p, a, tt, ul, g12
+
+
+def _dnn_inputs(device, ini_state, goal, dnn_out, u_last=None, gate12=None, with_gate=False):
+    """As _solve_inputs for the calls that take DNN1's output (B, 7) float32 in place of p_tra / a_tra / t:
+    (B, ini, goal, dnn_out, u_last, gate12)."""
+    f64 = torch.float64
+    ini = _dev_tensor(ini_state, (NX,), f64, device, "ini_state")
+    B = ini.shape[0]
+    named = {"goal": _dev_tensor(goal, (3,), f64, device, "goal"),
+             "dnn_out": _dev_tensor(dnn_out, (7,), torch.float32, device, "dnn_out"),
+             "u_last": _dev_tensor(u_last, (NU,), f64, device, "u_last", allow_none=True),
+             "gate12": _dev_tensor(gate12, (12,), f64, device, "gate12") if with_gate else None}
+    return (B, ini, *_same_batch(B, **named))
+
+
+@contextlib.contextmanager
+def _param_override(eng, field, value):
+    """Run the body with ``eng.params.<field> = value`` pushed through ``eng.set_params``; the saved value is put
+    back and pushed again on exit, also when the body raises.  ``value`` None or equal to the field: nothing."""
+    saved = getattr(eng.params, field)
+    if value is None or int(value) == int(saved):
+        yield
+        return
+    try:
+        setattr(eng.params, field, int(value))
+        eng.set_params(eng.params)
+        yield
+    finally:
+        setattr(eng.params, field, saved)
+        eng.set_params(eng.params)
 
 
 def _ptr(t):
@@ -184,25 +231,9 @@ class Engine:
         None keeps the context's parameter.  ``dtype=torch.float32`` uses the fp32 twin
         (lafse3_ocp_solve_f32: float32 buffers at the boundary, fp64 solve inside).
         """
-        if costate_option is not None and int(costate_option) != int(self.params.costate_option):
-            saved = self.params.costate_option
-            self.params.costate_option = int(costate_option)
-            self.set_params(self.params)
-            try:
-                return self.ocp_solve(ini_state, goal, p_tra, a_tra, t, u_last, want, dtype=dtype)
-            finally:
-                self.params.costate_option = saved
-                self.set_params(self.params)
         f32 = dtype == torch.float32
         d, f64 = self.device, (torch.float32 if f32 else torch.float64)
-        ini = _dev_tensor(ini_state, (NX,), f64, d, "ini_state")
-        B = ini.shape[0]
-        goal = _dev_tensor(goal, (3,), f64, d, "goal")
-        p = _dev_tensor(p_tra, (3,), f64, d, "p_tra")
-        a = _dev_tensor(a_tra, (3,), f64, d, "a_tra")
-        tt = torch.as_tensor(t, dtype=f64).to(d).reshape(-1).expand(B).contiguous()
-        ul = _dev_tensor(u_last, (NU,), f64, d, "u_last", allow_none=True)
-        goal, p, a, ul = _same_batch(B, goal=goal, p_tra=p, a_tra=a, u_last=ul)
+        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
         N = self.horizon
         out = {
             "x": torch.empty((B, N + 1, NX), dtype=f64, device=d) if "x" in want else None,
@@ -213,10 +244,11 @@ class Engine:
             "iters": torch.empty((B,), dtype=torch.int32, device=d),
         }
         fn = self._L.lafse3_ocp_solve_f32 if f32 else self._L.lafse3_ocp_solve
-        check(fn(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
-                 _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]), _ptr(out["cost"]),
-                 _ptr(out["status"]), _ptr(out["iters"]), self._stream()),
-              "lafse3_ocp_solve_f32" if f32 else "lafse3_ocp_solve")
+        with _param_override(self, "costate_option", costate_option):
+            check(fn(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
+                     _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]), _ptr(out["cost"]),
+                     _ptr(out["status"]), _ptr(out["iters"]), self._stream()),
+                  "lafse3_ocp_solve_f32" if f32 else "lafse3_ocp_solve")
         return {k: v for k, v in out.items() if v is not None}
 
     def ocp_sensitivity(self, ini_state, goal, p_tra, a_tra, t, u_last=None, want=("x", "u", "dx", "du")):
@@ -229,14 +261,7 @@ class Engine:
           (dx and du of such an instance are zero).
         The derivative is that of the barrier problem at the final mu (include/lafse3.h).  float64 only."""
         d, f64 = self.device, torch.float64
-        ini = _dev_tensor(ini_state, (NX,), f64, d, "ini_state")
-        B = ini.shape[0]
-        goal = _dev_tensor(goal, (3,), f64, d, "goal")
-        p = _dev_tensor(p_tra, (3,), f64, d, "p_tra")
-        a = _dev_tensor(a_tra, (3,), f64, d, "a_tra")
-        tt = torch.as_tensor(t, dtype=f64).to(d).reshape(-1).expand(B).contiguous()
-        ul = _dev_tensor(u_last, (NU,), f64, d, "u_last", allow_none=True)
-        goal, p, a, ul = _same_batch(B, goal=goal, p_tra=p, a_tra=a, u_last=ul)
+        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
         N = self.horizon
         shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,),
                   "dx": (B, 7, N + 1, NX), "du": (B, 7, N, NU)}
@@ -254,15 +279,7 @@ class Engine:
     def objective(self, ini_state, goal, gate12, p_tra, a_tra, t, u_last=None):
         """Batched run_quad.objective -> (reward (B,), status (B,))."""
         d, f64 = self.device, torch.float64
-        ini = _dev_tensor(ini_state, (NX,), f64, d, "ini_state")
-        B = ini.shape[0]
-        goal = _dev_tensor(goal, (3,), f64, d, "goal")
-        g12 = _dev_tensor(gate12, (12,), f64, d, "gate12")
-        p = _dev_tensor(p_tra, (3,), f64, d, "p_tra")
-        a = _dev_tensor(a_tra, (3,), f64, d, "a_tra")
-        tt = torch.as_tensor(t, dtype=f64).to(d).reshape(-1).expand(B).contiguous()
-        ul = _dev_tensor(u_last, (NU,), f64, d, "u_last", allow_none=True)
-        goal, g12, p, a, ul = _same_batch(B, goal=goal, gate12=g12, p_tra=p, a_tra=a, u_last=ul)
+        B, ini, goal, p, a, tt, ul, g12 = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last, gate12, True)
         R = torch.empty((B,), dtype=f64, device=d)
         st = torch.empty((B,), dtype=torch.int32, device=d)
         check(self._L.lafse3_objective(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(g12), _ptr(p), _ptr(a), _ptr(tt),
@@ -276,28 +293,14 @@ class Engine:
         six sensitivity sweeps, lafse3.h).  ``verify``: wait for the launch and raise Lafse3Error when a probe
         task was lost (its out8 row would carry a NaN into the DNN1 update); False leaves the launch
         asynchronous -- the caller then checks (check_device / last_counters) before using out8."""
-        if grad_mode is not None and int(grad_mode) != int(self.params.grad_mode):
-            saved = self.params.grad_mode
-            self.params.grad_mode = int(grad_mode)
-            self.set_params(self.params)
-            try:
-                return self.sol_gradient(ini_state, goal, gate12, dnn_out, u_last, want_rewards, verify=verify)
-            finally:
-                self.params.grad_mode = saved
-                self.set_params(self.params)
         d, f64 = self.device, torch.float64
-        ini = _dev_tensor(ini_state, (NX,), f64, d, "ini_state")
-        B = ini.shape[0]
-        goal = _dev_tensor(goal, (3,), f64, d, "goal")
-        g12 = _dev_tensor(gate12, (12,), f64, d, "gate12")
-        dnn = _dev_tensor(dnn_out, (7,), torch.float32, d, "dnn_out")
-        ul = _dev_tensor(u_last, (NU,), f64, d, "u_last", allow_none=True)
-        goal, g12, dnn, ul = _same_batch(B, goal=goal, gate12=g12, dnn_out=dnn, u_last=ul)
+        B, ini, goal, dnn, ul, g12 = _dnn_inputs(d, ini_state, goal, dnn_out, u_last, gate12, True)
         out8 = torch.empty((B, 8), dtype=f64, device=d)
         R9 = torch.empty((B, 9), dtype=f64, device=d) if want_rewards else None
         S9 = torch.empty((B, 9), dtype=torch.int32, device=d) if want_rewards else None
-        check(self._L.lafse3_sol_gradient(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(g12), _ptr(dnn), _ptr(ul),
-                                          _ptr(out8), _ptr(R9), _ptr(S9), self._stream()), "lafse3_sol_gradient")
+        with _param_override(self, "grad_mode", grad_mode):
+            check(self._L.lafse3_sol_gradient(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(g12), _ptr(dnn), _ptr(ul),
+                                              _ptr(out8), _ptr(R9), _ptr(S9), self._stream()), "lafse3_sol_gradient")
         if verify:
             self.check_device()
         if want_rewards:
@@ -356,12 +359,7 @@ class Engine:
     def get_input(self, ini_state, goal, dnn_out, u_last=None, want_x=False):
         """Batched run_quad.get_input: first control (B,4) [+ state trajectory (B,N+1,13)]."""
         d, f64 = self.device, torch.float64
-        ini = _dev_tensor(ini_state, (NX,), f64, d, "ini_state")
-        B = ini.shape[0]
-        goal = _dev_tensor(goal, (3,), f64, d, "goal")
-        dnn = _dev_tensor(dnn_out, (7,), torch.float32, d, "dnn_out")
-        ul = _dev_tensor(u_last, (NU,), f64, d, "u_last", allow_none=True)
-        goal, dnn, ul = _same_batch(B, goal=goal, dnn_out=dnn, u_last=ul)
+        B, ini, goal, dnn, ul, _ = _dnn_inputs(d, ini_state, goal, dnn_out, u_last)
         u0 = torch.empty((B, NU), dtype=f64, device=d)
         x = torch.empty((B, self.horizon + 1, NX), dtype=f64, device=d) if want_x else None
         st = torch.empty((B,), dtype=torch.int32, device=d)

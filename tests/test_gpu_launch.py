@@ -7,7 +7,9 @@
   * the probe-queue guard: a sample push withheld by the debug hook is reported (LAFSE3_EDEVICE, status 7,
     NaN rewards) instead of leaving a stale out8;
   * lafse3_record_iters refuses a launch larger than its buffer; lafse3_reward scores B > slots trajectories;
-  * two contexts on two streams with overlapping launches give the single-launch outputs bit for bit.
+  * two contexts on two streams with overlapping launches give the single-launch outputs bit for bit;
+  * the host layer: regrown device buffers keep results, a NULL required pointer is refused before any launch,
+    scoring leaves lafse3_record_iters alone, and no entry point moves the caller's current device (two GPUs).
 """
 import numpy as np
 import pytest
@@ -201,3 +203,136 @@ def test_two_launches_in_flight_equal_single_launches(eng):
         ref = ref_a if i % 2 == 0 else ref_b
         for k in ("x", "u", "lam", "cost", "status", "iters"):
             assert torch.equal(o[k], ref[k]), (i, k)
+
+
+def _batch6():
+    from learningagileflight_se3_amd import scenario as S
+    sb = S.synthetic_batch(6, seed=7)
+    sb["p"] = sb["dnn_out"][:, :3].astype(np.float64)
+    sb["a"] = sb["dnn_out"][:, 3:6].astype(np.float64)
+    sb["t"] = sb["dnn_out"][:, 6].astype(np.float64)
+    return sb
+
+
+def test_buffer_growth_keeps_results():
+    """The context's grow-only device buffers are freed and reallocated while earlier launches' outputs are still
+    in flight; results must not change.  On a fresh context: the fp32 twin on 2 samples, then on 6 (regrows its
+    staging buffer); get_input on 2, sol_gradient without rewards9 on 6 (shares the scratch: 54 doubles, inside
+    the 400 get_input took), get_input on 6 (regrows the scratch), get_input on 2 again.  Rows 0-1 agree bit for
+    bit throughout and the device check is clean."""
+    from learningagileflight_se3_amd.engine import Engine
+    sb = _batch6()
+    solve = [sb[k].astype(np.float32) for k in ("ini", "goal", "p", "a", "t")]
+    e = Engine()
+    try:
+        f2 = e.ocp_solve(*(v[:2] for v in solve), dtype=torch.float32)
+        f6 = e.ocp_solve(*solve, dtype=torch.float32)
+        u2, s2 = e.get_input(sb["ini"][:2], sb["goal"][:2], sb["dnn_out"][:2])
+        out8 = e.sol_gradient(sb["ini"], sb["goal"], sb["gate12"], sb["dnn_out"])
+        u6, s6 = e.get_input(sb["ini"], sb["goal"], sb["dnn_out"])
+        u2b, s2b = e.get_input(sb["ini"][:2], sb["goal"][:2], sb["dnn_out"][:2])
+        torch.cuda.synchronize()
+        e.check_device()
+        for k in ("x", "u", "lam", "cost", "status", "iters"):
+            assert f2[k].dtype == (torch.int32 if k in ("status", "iters") else torch.float32)
+            assert torch.equal(f2[k], f6[k][:2]), k
+        assert torch.all(f6["status"] <= 1) and torch.all(torch.isfinite(f6["x"]))
+        assert torch.equal(u2, u2b) and torch.equal(s2, s2b)
+        assert torch.equal(u2, u6[:2]) and torch.equal(s2, s6[:2])
+        assert torch.all(torch.isfinite(u6)) and torch.all(torch.isfinite(out8))
+    finally:
+        e.close()
+
+
+# required pointer arguments of the solver and scoring entry points, as positions after (ctx, B)
+_REQUIRED = {
+    "lafse3_ocp_solve": (0, 1, 2, 3, 4), "lafse3_ocp_solve_f32": (0, 1, 2, 3, 4),
+    "lafse3_ocp_sensitivity": (0, 1, 2, 3, 4), "lafse3_objective": (0, 1, 2, 3, 4, 5, 7),
+    "lafse3_sol_gradient": (0, 1, 2, 3, 5), "lafse3_get_input": (0, 1, 3, 4), "lafse3_reward": (0, 1, 2, 3),
+    "lafse3_traversal_time": (0, 1, 2, 3, 5, 6),
+}
+
+
+def test_null_required_pointer_is_rejected_before_any_launch(eng):
+    """Each solver entry point, called through the C ABI on a live context with B = 2 and one required pointer
+    NULL, returns LAFSE3_EINVAL, and launches nothing: lafse3_last_kernel_ms still reports the earlier solve."""
+    import ctypes
+    from learningagileflight_se3_amd import _lib
+    sb = _batch6()
+    eng.ocp_solve(sb["ini"][:2], sb["goal"][:2], sb["p"][:2], sb["a"][:2], sb["t"][:2])
+    ms = eng.last_kernel_ms()
+    assert ms > 0
+    # every non-NULL pointer is this buffer: larger than any argument at B = 2, should a check let a launch through
+    buf = torch.zeros(16384, dtype=torch.float64, device=eng.device)
+    for name, required in _REQUIRED.items():
+        argtypes = _lib.SIGNATURES[name][1][2:]
+        full = [0.0 if a is ctypes.c_double else ctypes.c_void_p(buf.data_ptr()) for a in argtypes]
+        full[-1] = eng._stream()
+        for i in required:
+            args = list(full)
+            args[i] = None
+            assert getattr(eng._L, name)(eng._ctx, 2, *args) == -1, (name, i)
+            assert eng._L.lafse3_last_error(), (name, i)
+    assert eng.last_kernel_ms() == ms
+    torch.cuda.synchronize()
+    assert not buf.any()
+    eng.check_device()
+
+
+def test_scoring_leaves_iteration_recording_alone(eng):
+    """lafse3_reward is a scoring launch: with lafse3_record_iters armed it neither fails on the buffer's capacity
+    (13 trajectories against 6 entries) nor writes it; the next solve without an iters argument of its own fills it
+    with the counts the same solve returns through Engine.ocp_solve."""
+    sb = _batch6()
+    B = 6
+    dev = [torch.as_tensor(np.ascontiguousarray(sb[k], dtype=np.float64), device=eng.device)
+           for k in ("ini", "goal", "p", "a", "t")]
+    ref = eng.ocp_solve(*dev)
+    rep = np.arange(13) % B
+    buf = torch.full((B,), -1, dtype=torch.int32, device=eng.device)
+    eng.record_iters(buf)
+    try:
+        R = eng.reward(ref["x"].cpu().numpy()[rep], sb["goal"][rep], sb["gate12"][rep])
+        torch.cuda.synchronize()
+        assert torch.all(torch.isfinite(R)) and torch.all(buf == -1)
+        st = torch.empty((B,), dtype=torch.int32, device=eng.device)
+        ptrs = [v.data_ptr() for v in dev] + [None] * 5 + [st.data_ptr(), None]     # no u_last, outputs: status only
+        assert eng._L.lafse3_ocp_solve(eng._ctx, B, *ptrs, eng._stream()) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(buf, ref["iters"]) and torch.all(buf > 0) and torch.equal(st, ref["status"])
+    finally:
+        eng.record_iters(None)
+
+
+def test_no_entry_point_moves_the_current_device():
+    """include/lafse3.h: no entry point changes the calling thread's current HIP device.  A context and a
+    QueueStream bound to device 1 are created, used and destroyed while torch's current device stays 0."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two HIP devices (a context bound to a device other than the current one)")
+    from learningagileflight_se3_amd.engine import Engine, QueueStream
+    sb = _batch6()
+    torch.cuda.set_device(0)
+
+    def still_0(what):
+        assert torch.cuda.current_device() == 0, what
+
+    e = Engine(device=1)
+    try:
+        still_0("Engine()")
+        out = e.ocp_solve(sb["ini"], sb["goal"], sb["p"], sb["a"], sb["t"])
+        still_0("ocp_solve")
+        assert out["x"].device.index == 1
+        assert e.last_counters()["iterations"] > 0
+        still_0("last_counters")
+        e.last_resto_counters()
+        still_0("last_resto_counters")
+        e.check_device()
+        still_0("check_device")
+        q = QueueStream(device=1)
+        still_0("QueueStream()")
+        q.close()
+        still_0("QueueStream.close")
+        assert torch.all(out["status"].cpu() <= 1)
+    finally:
+        e.close()
+    still_0("Engine.close")

@@ -228,25 +228,26 @@ def test_queue_streams_overlap_two_contexts(eng):
     torch.cuda.synchronize()
     single_s = eng.last_kernel_ms() / 1e3
     e2 = Engine()
-    qs = [QueueStream(), QueueStream()]
-    try:
-        for e, q in ((eng, qs[0]), (e2, qs[1])):   # warm both contexts on their streams
-            with torch.cuda.stream(q.stream):
-                e.ocp_solve(*args)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        outs = []
-        for e, q in ((eng, qs[0]), (e2, qs[1])):
-            with torch.cuda.stream(q.stream):
-                outs.append(e.ocp_solve(*args))
-        torch.cuda.synchronize()
-        both_s = time.perf_counter() - t0
-    finally:
-        for q in qs:
-            q.close()
-    # the contexts outlive the streams they launched on: counters and the device check read on a stream of the
-    # context's own (api.hip read_counters), not on the destroyed launch stream
-    try:
+    qs = []
+    try:                                           # e2 is closed whatever fails below
+        qs = [QueueStream(), QueueStream()]
+        try:
+            for e, q in ((eng, qs[0]), (e2, qs[1])):   # warm both contexts on their streams
+                with torch.cuda.stream(q.stream):
+                    e.ocp_solve(*args)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            outs = []
+            for e, q in ((eng, qs[0]), (e2, qs[1])):
+                with torch.cuda.stream(q.stream):
+                    outs.append(e.ocp_solve(*args))
+            torch.cuda.synchronize()
+            both_s = time.perf_counter() - t0
+        finally:
+            for q in qs:
+                q.close()
+        # the contexts outlive the streams they launched on: counters and the device check read on a stream of the
+        # context's own (api.hip read_counters), not on the destroyed launch stream
         for e in (eng, e2):
             assert e.last_counters()["iterations"] > 0
             e.check_device()
