@@ -210,13 +210,38 @@ int lafse3_check_device(lafse3_ctx *ctx);
  * restoration phase, counters[1] returns to the original problem (entries - returns ended the solve with
  * status 2, 4, 6, 8 or 9).  Read back synchronously; EDEVICE as lafse3_last_counters. */
 int lafse3_last_resto_counters(lafse3_ctx *ctx, int64_t counters[2]);
-/* Debug: subsequent launches write, per instance and per IPM iteration (< iters), 16 doubles
- * [mu, E0, theta, phi, gradphi.d, alpha_max, alpha_z, alpha, delta_w, accepted, filter_size, sweeps,
- *  refinement ratio 0/1/2, refinement count] to the device buffer buf (instances x iters x 16).
- * buf = NULL disables. */
+/* Debug: subsequent launches write, per instance and per IPM iteration (< iters), 16 doubles to the device buffer
+ * buf (instances x iters x 16):
+ *    0 mu                 barrier parameter of the iteration
+ *    1 E0                 overall NLP error (mu = 0) at the iterate
+ *    2 theta              constraint violation at the iterate
+ *    3 phi                barrier objective at the iterate
+ *    4 gradphi.d          directional derivative of phi along the step
+ *    5 alpha_max          fraction-to-the-boundary primal step
+ *    6 alpha_z            dual step
+ *    7 alpha              accepted primal step
+ *    8 delta_w            inertia regularisation the step was computed with (0: none was needed)
+ *    9 accepted           1 when the line search accepted a trial point
+ *   10 filter_size        entries of the filter after the iteration
+ *   11 sweeps             Riccati sweeps so far (cumulative)
+ *   12 ratio 0            residual ratio of the step before iterative refinement
+ *   13 ratio 1            residual ratio after the first refinement sweep (-1: none)
+ *   14 J                  unscaled objective at the iterate
+ *   15 barrier log sum    sum of log(v - lo) + log(hi - v) over the bounded variables at the iterate
+ * Iterations spent inside a restoration phase write no row.  buf = NULL disables. */
 int lafse3_debug_trace(lafse3_ctx *ctx, double *buf, int iters);
-/* Debug: dump the Newton step [dx (51x13) | du (50x4) | lam+ (50x13)] of IPM iteration `it`
- * (before or after iterative refinement) into buf (instances x 1513).  buf = NULL disables. */
+/* Debug: dump the Newton step of IPM iteration `it` (before or after iterative refinement) and the iterate the
+ * Newton system was formed at into buf (instances x 3732).  One record, every array stage-major and padded to
+ * LAFSE3_MAX_N stages (entries of stages beyond the horizon are not written):
+ *   the step     dx (51x13) | du (50x4) | lam+ (50x13)                                          1513 doubles
+ *   the iterate  x (51x13) | u (50x4) | lam (50x13) | zLu (50x4) | zUu (50x4) | zLw (51x3) | zUw (51x3)
+ * in the solver's internal quantities: lam+ and lam are multipliers of the problem whose objective is scaled by
+ * s_obj (the multipliers lafse3_ocp_solve returns are lam / s_obj), zL / zU the bound duals of u and of omega
+ * (stage 0, which is fixed, has zLw = zUw = 0).  mu and delta_w of that iteration are words 0 and 8 of
+ * lafse3_debug_trace.  With an inertia retry the pre-refinement record is that of the last retry.
+ * The iterate is written by lafse3_ocp_solve / lafse3_ocp_solve_f32 launches, which run a kernel of their own while
+ * a dump is armed (the extra stores are compiled out of the production kernel); the other entry points write the step
+ * only, at the same stride of 3732 doubles per instance.  buf = NULL disables. */
 int lafse3_debug_dump(lafse3_ctx *ctx, double *buf, int it, int after_refine);
 /* Debug: per-instance record of 32 x uint64 into buf (instances x 32).  The timer build (-DLAFSE3_PHASE_TIMERS)
  * fills columns 0..15 and 24..31, every build the placement record 16..23: 12 phase timers in s_memtime cycles (init, errors, table, backward, forward, adjoint, residual, refine-backward,

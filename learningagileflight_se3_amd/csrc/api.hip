@@ -373,7 +373,10 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
     }
     (void)hipEventRecord(c->ev0, st);
     // the sensitivity pass is compiled into a kernel of its own (ipm_kernel.hip ipm_kernel_sens)
+    // and so are the extra stores of a debug dump that carries the iterate (ipm_kernel_dump: plain solves only)
     if (sens) hipLaunchKernelGGL(lafse3::ipm_kernel_sens, dim3((unsigned)grid), dim3(64), 0, st, A, *sens);
+    else if (A.dump && A.mode == lafse3::MODE_SOLVE && !A.sched)
+        hipLaunchKernelGGL(lafse3::ipm_kernel_dump, dim3((unsigned)grid), dim3(64), 0, st, A);
     else hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
     e = hipGetLastError();
     (void)hipEventRecord(c->ev1, st);

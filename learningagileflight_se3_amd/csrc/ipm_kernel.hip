@@ -40,7 +40,10 @@ constexpr int WAVE = 64;
 __device__ inline int lane_id() { return (int)(threadIdx.x & (WAVE - 1)); }
 __device__ inline int64_t slot_id() { return (int64_t)blockIdx.x; }
 constexpr int TRACE_W = 16;
-constexpr int DUMP_W = (MAXN + 1) * NX + MAXN * NU + MAXN * NX;
+// debug dump record: the step [dx | du | lam+], then the iterate [x | u | lam | zLu | zUu | zLw | zUw] (dump_point)
+constexpr int DUMP_STEP_W = (MAXN + 1) * NX + MAXN * NU + MAXN * NX;
+constexpr int DUMP_W = 2 * DUMP_STEP_W + 2 * MAXN * NU + 2 * (MAXN + 1) * 3;
+static_assert(DUMP_W == 3732, "lafse3.h documents the dump record as 3732 doubles per instance");
 
 enum Mode : int { MODE_SOLVE = 0, MODE_OBJECTIVE = 1, MODE_GRAD = 2, MODE_GETINPUT = 3, MODE_REWARD = 4 };
 enum { ST_SOLVED = 0, ST_ACCEPTABLE = 1, ST_MAXITER = 2, ST_LS_FAIL = 3, ST_NONFINITE = 4, ST_TINY = 5,
@@ -435,6 +438,32 @@ __device__ inline void bar_terms(double v, double lo, double hi, double zl, doub
     double sl = v - lo, su = hi - v;
     g = -mu / sl + mu / su;
     sg = zl / sl + zu / su;
+}
+
+// Second part of the dump record, behind the step arrays: the iterate at which the dumped Newton system was formed
+// (the point before the step is taken), x | u | lam | zLu | zUu | zLw | zUw, stage-major and padded to MAXN like the step.  Called by ipm_kernel_dump only (run_instance<.., true>): written from linear_solve or
+// from ipm_kernel's iteration loop, inlined or as a call, it changed the register allocation of the hot sweeps
+// (+1.6 % kernel time with one cold call inside linear_solve).
+__device__ __noinline__ void dump_point(const Smem &S, const gdouble *ws, int N, double *out)
+{
+    const int lane = lane_id();
+    WS_TRAJ(ws);
+    const auto *lam = LAM;
+    for (int e = lane; e < (N + 1) * NX; e += WAVE) out[e] = S.x[(e % NX) * SX + e / NX];
+    out += (MAXN + 1) * NX;
+    for (int e = lane; e < N * NU; e += WAVE) out[e] = S.u[(e % NU) * SX + e / NU];
+    out += MAXN * NU;
+    for (int e = lane; e < N * NX; e += WAVE) out[e] = lam[(e % NX) * SX + e / NX];
+    out += MAXN * NX;
+    for (int e = lane; e < N * NU; e += WAVE) {
+        out[e] = ZLU[(e % NU) * SX + e / NU];
+        out[MAXN * NU + e] = ZUU[(e % NU) * SX + e / NU];
+    }
+    out += 2 * MAXN * NU;
+    for (int e = lane; e < (N + 1) * 3; e += WAVE) {
+        out[e] = ZLW[(e % 3) * SX + e / 3];
+        out[(MAXN + 1) * 3 + e] = ZUW[(e % 3) * SX + e / 3];
+    }
 }
 
 __device__ void dump_step(const Smem &S, const gdouble *ws, int N, double *out)
@@ -1783,7 +1812,8 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 // One NLP instance (or one scored trajectory) on this wave, with the workspace slot ws.
 // Returns the instance's IPM iteration count (0 for trajectory scoring).
 // SENS (ipm_kernel_sens): the sensitivity pass of sens.inc follows a MODE_SOLVE instance; ipm_kernel compiles none of it.
-template <bool SENS>
+// DUMP (ipm_kernel_dump): the debug dump also records the iterate (dump_point); ipm_kernel compiles none of that.
+template <bool SENS, bool DUMP = false>
 __device__ __attribute__((always_inline)) inline int run_instance(const KernelArgs &A, Smem &S, const int64_t inst,
                                                                  gdouble *ws, const SensArgs *Z = nullptr)
 {
@@ -2073,6 +2103,8 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
         PT_END(S, 11);
         double dw = 0.0;
         double ratios[4] = {0, 0, 0, 0};
+        if constexpr (DUMP)   // the iterate of this iteration's Newton system (it does not change until accept_step)
+            if (A.dump && it == A.dump_it) dump_point(S, ws, N, A.dump + inst * (int64_t)DUMP_W + DUMP_STEP_W);
         double *dpre = (A.dump && it == A.dump_it && !A.dump_refine) ? A.dump + inst * (int64_t)DUMP_W : nullptr;
         int ok = linear_solve(M, at, S, C, ws, 0.0, 1, 0, 1, 0, sweeps, ratios, dpre);
         if (!ok) {
@@ -2621,6 +2653,25 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_sens(KernelArgs A, SensArgs 
         KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         __asm__ volatile("" : "+s"(Ap));
         run_instance<true>(*(const KernelArgs *)Ap, S, inst, ws, &Z);
+    }
+}
+
+// The persistent solver whose debug dump carries the iterate (lafse3_debug_dump armed, lafse3_ocp_solve launches): as
+// ipm_kernel_sens a further instantiation of run_instance in a kernel of its own with the plain queue-head loop, so
+// that ipm_kernel's code is what it is without the extra stores.
+__global__ __launch_bounds__(64, 1) void ipm_kernel_dump(KernelArgs A)
+{
+    Smem &S = instance_smem();
+    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
+    for (;;) {
+        unsigned long long v = 0ull;
+        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
+        const int64_t inst = bcast_i64((int64_t)v);
+        if (inst >= A.n_inst) break;
+        typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
+        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+        __asm__ volatile("" : "+s"(Ap));
+        run_instance<false, true>(*(const KernelArgs *)Ap, S, inst, ws);
     }
 }
 

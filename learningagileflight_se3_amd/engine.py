@@ -191,7 +191,10 @@ class Engine:
         check(self._L.lafse3_debug_trace(self._ctx, _ptr(buf), int(iters)), "lafse3_debug_trace")
 
     def debug_dump(self, buf=None, it: int = -1, after_refine: bool = False):
-        """Debug: Newton step of iteration `it` into a (instances, 1513) float64 device tensor."""
+        """Debug: Newton step of iteration `it` (before or after iterative refinement) and the iterate it was
+        computed at into a (instances, 3732) float64 device tensor: [dx 51x13 | du 50x4 | lam+ 50x13] then
+        [x 51x13 | u 50x4 | lam 50x13 | zLu 50x4 | zUu 50x4 | zLw 51x3 | zUw 51x3], stage-major, padded to 50
+        stages, multipliers of the scaled-objective problem (lafse3_debug_dump in lafse3.h).  None disables."""
         self._dump_buf = buf
         check(self._L.lafse3_debug_dump(self._ctx, _ptr(buf), int(it), int(after_refine)), "lafse3_debug_dump")
 

@@ -47,6 +47,10 @@
 #define NMAX 64
 #define FILTER_MAX 64
 #define NMAX_DUMP 50
+/* per-instance record of orc_debug_dump: the step [dx | du | lam+] and the iterate it was computed at
+ * [x | u | lam | zLu | zUu | zLw | zUw], each padded to NMAX_DUMP stages */
+#define DUMP_STEP_W ((NMAX_DUMP + 1) * NX + NMAX_DUMP * NU + NMAX_DUMP * NX)
+#define DUMP_W (2 * DUMP_STEP_W + 2 * NMAX_DUMP * NU + 2 * (NMAX_DUMP + 1) * 3)
 
 typedef struct {
     /* model (quad_policy.py:37, quad_model.py:37) */
@@ -870,6 +874,21 @@ static void dump_step(const orc_ws *W, double *out)
     memcpy(out, W->dx, sizeof(double) * (W->N + 1) * NX);
     memcpy(out + (NMAX_DUMP + 1) * NX, W->du, sizeof(double) * W->N * NU);
     memcpy(out + (NMAX_DUMP + 1) * NX + NMAX_DUMP * NU, W->lamp, sizeof(double) * W->N * NX);
+    /* the iterate the system was formed at (internal, scaled-objective quantities) */
+    double *pt = out + DUMP_STEP_W;
+    memcpy(pt, W->x, sizeof(double) * (W->N + 1) * NX);
+    pt += (NMAX_DUMP + 1) * NX;
+    memcpy(pt, W->u, sizeof(double) * W->N * NU);
+    pt += NMAX_DUMP * NU;
+    memcpy(pt, W->lam, sizeof(double) * W->N * NX);
+    pt += NMAX_DUMP * NX;
+    memcpy(pt, W->zLu, sizeof(double) * W->N * NU);
+    pt += NMAX_DUMP * NU;
+    memcpy(pt, W->zUu, sizeof(double) * W->N * NU);
+    pt += NMAX_DUMP * NU;
+    memcpy(pt, W->zLw, sizeof(double) * (W->N + 1) * 3);
+    pt += (NMAX_DUMP + 1) * 3;
+    memcpy(pt, W->zUw, sizeof(double) * (W->N + 1) * 3);
 }
 
 /* IPOPT's iterative refinement of a computed solution (min 1, max 10 steps; stop at residual ratio
@@ -2851,7 +2870,7 @@ int orc_solve_q(const orc_params *P, int64_t B, const double *ini, const double 
         W->N = N;
         W->trace = g_trace ? g_trace + b * (int64_t)g_trace_iters * 16 : NULL;
         W->trace_iters = g_trace_iters;
-        W->dump = g_dump ? g_dump + b * (int64_t)((NMAX_DUMP + 1) * NX + NMAX_DUMP * NU + NMAX_DUMP * NX) : NULL;
+        W->dump = g_dump ? g_dump + b * (int64_t)DUMP_W : NULL;
         W->dump_it = g_dump_it;
         W->dump_refine = g_dump_refine;
         orc_inst I;

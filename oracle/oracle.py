@@ -234,15 +234,18 @@ def assemble(R9, dnn_out, params=None):
     return out8
 
 
-def debug_trace(buf=None, iters=0):
-    """Debug: per-iteration trace of subsequent solve() calls into buf (B, iters, 12)."""
+def debug_trace(buf=None, iters=0, fast=False):
+    """Debug: per-iteration trace of subsequent solve() calls into buf (B, iters, 16), the words of
+    lafse3_debug_trace (lafse3.h).  fast=True arms the -O3 / FMA build (solve(fast=True))."""
     global _trace_keep
     _trace_keep = buf
-    lib().orc_debug_trace(_ptr(buf), int(iters))
+    lib(fast).orc_debug_trace(_ptr(buf), int(iters))
 
 
 def debug_dump(buf=None, it=-1, after_refine=False):
-    """Debug: Newton step [dx 51x13 | du 50x4 | lam+ 50x13] of iteration `it` into buf (B, 1513)."""
+    """Debug: Newton step [dx 51x13 | du 50x4 | lam+ 50x13] of iteration `it` and the iterate it was computed at
+    [x 51x13 | u 50x4 | lam 50x13 | zLu 50x4 | zUu 50x4 | zLw 51x3 | zUw 51x3] into buf (B, DUMP_W = 3732), the
+    record of lafse3_debug_dump (lafse3.h)."""
     global _dump_keep
     _dump_keep = buf
     lib().orc_debug_dump(_ptr(buf), int(it), int(after_refine))

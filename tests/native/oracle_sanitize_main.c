@@ -67,7 +67,8 @@ int main(int argc, char **argv)
         memcpy(qn + 4 * b, q + b * 36, sizeof(double) * 4);
         tn[b] = t[b * 9];
     }
-    double *trace = calloc(8 * 64, sizeof(double)), *dump = calloc(8192, sizeof(double));
+    /* one instance's dump record (step + iterate), exactly: a write past it is a sanitizer report */
+    double *trace = calloc(8 * 64, sizeof(double)), *dump = calloc(DUMP_W, sizeof(double));
     orc_debug_trace(trace, 8);
     orc_debug_dump(dump, 3, 1);
     bad |= orc_solve_q(&P, 1, ini, goal, pn, qn, tn, NULL, x, u, lam, cost, st, cnt);

@@ -279,19 +279,72 @@ def test_edge_cases(eng, batch):
 
 
 def test_shorter_horizon(batch):
+    """Horizons 1, 2, 3, 7, 20, 49 (the lane-per-stage guards lane < N, lane <= N, min(k + 1, N - 1), max(k - 1, 0) at
+    their edges), 8 samples each, t = 0.5 N dt so that the traversal weight lies inside the horizon: the comparison of
+    test_ocp_solve_matches_oracle_and_is_kkt, same rule and tolerances, the count of equal iteration paths held to
+    the rounding yardstick less 2 % over the 48 solves together.  The count is taken over the solves that the oracle's
+    own FMA build solves with its strict build's decisions (yardstick.solve_decisions: mu, delta_w, accepted, filter
+    size, step halvings of every iteration): where rounding alone moves a decision of the oracle, the device's path is
+    not held to it.  That leaves out one solve, N = 20, sample 6, and this is what was measured on it (debug traces of
+    all three, strict oracle 141 iterations ending acceptable, FMA build 141, device 161):
+      * the continuous trace words (E0, theta, phi, grad phi.d, alpha_max, alpha_z, J, log sum) of the device and of
+        the FMA build leave the strict build's at the same rate: 4e-15 at iteration 0, 6e-13 at 10, 5e-11 at 40, 5e-8 at
+        70, 9e-7 at 90 (90 iterations at mu = 0.1 with steps of 1e-3 .. 1e-1 and delta_w of 10 .. 300), the device
+        within a factor of 1.5 of the FMA build's figure at every one of them; every decision agrees up to iteration 125;
+      * at mu = 2.5e-9, theta = 7e-9 the inertia verdict on K(0) is a near tie: the device regularises
+        (delta_w = 113.8) at iteration 126, the strict build at 127, the FMA build at 128, one after the other.
+        From there the three paths are different solves; the FMA build happens to end after 141 iterations too, which
+        is why status and iteration count (yardstick.solve_paths) do not show its flip.
+    The N = 20 cost assertion of this test has always contained that sample, and every other assertion here (statuses,
+    cost to 1e-6, KKT certificate) still covers it.  First run: 47 of 47 paths equal, yardstick 47 of 47.
+    The oracle converges (status <= 1) on all 48, N = 1 included, so no sample was replaced."""
     from learningagileflight_se3_amd.engine import Engine
     from oracle import oracle as O
-    e = Engine(horizon=20)
+    import kkt
     sb = batch
     B = 8
     p = sb["dnn_out"][:B, :3].astype(np.float64)
     a = sb["dnn_out"][:B, 3:6].astype(np.float64)
-    t = np.full(B, 1.0)
-    out = e.ocp_solve(sb["ini"][:B], sb["goal"][:B], p, a, t)
     q = np.stack([O.rd2quat(ai) for ai in a])
-    ref = O.solve(sb["ini"][:B], sb["goal"][:B], p, q, t, params=O.default_params(horizon=20))
-    assert out["x"].shape == (B, 21, 13)
-    assert np.max(np.abs(out["cost"].cpu().numpy() - ref["cost"]) / ref["cost"]) < 1e-6
+    n_same = n_yard = n_kept = 0
+    for N in (1, 2, 3, 7, 20, 49):
+        e = Engine(horizon=N)
+        t = np.full(B, 0.5 * N * 0.1)
+        out = e.ocp_solve(sb["ini"][:B], sb["goal"][:B], p, a, t)
+        torch.cuda.synchronize()
+        g = {k: v.cpu().numpy() for k, v in out.items()}
+        ref = O.solve(sb["ini"][:B], sb["goal"][:B], p, q, t, params=O.default_params(horizon=N))
+        assert g["x"].shape == (B, N + 1, 13) and g["u"].shape == (B, N, 4) and g["lam"].shape == (B, N, 13), N
+        assert np.all(g["status"] <= 1) and np.all(ref["status"] <= 1), (N, g["status"], ref["status"])
+        if N == 20:
+            assert out["x"].shape == (B, 21, 13)
+            assert np.max(np.abs(out["cost"].cpu().numpy() - ref["cost"]) / ref["cost"]) < 1e-6
+        same = g["iters"] == ref["iters"]
+        ns = int(same.sum())
+        yargs, ykw = (sb["ini"][:B], sb["goal"][:B], p, q, t), {"params": O.default_params(horizon=N)}
+        kept = yardstick.solve_decisions(yargs, ykw, ref)
+        n_kept += int(kept.sum())
+        n_same += int((same & kept).sum())
+        n_yard += yardstick.solve_paths(tuple(v[kept] for v in yargs), ykw, {k: v[kept] for k, v in ref.items()})
+        print(f"N={N}: same iteration path {ns}/{B}, iterations {g['iters'].tolist()}, oracle's decisions stable "
+              f"under rounding on {kept.astype(int).tolist()}")
+        if ns:
+            for k in ("x", "u"):
+                d = np.abs(g[k][same] - ref[k][same]) / (1 + np.abs(ref[k][same]))
+                assert d.max() < 1e-6, (N, k)
+            assert np.max(np.abs(g["cost"][same] - ref["cost"][same]) / np.abs(ref["cost"][same])) < 1e-10, N
+            dl = np.abs(g["lam"][same] - ref["lam"][same]).reshape(ns, -1).max(1)
+            assert np.max(dl / (1 + np.abs(ref["lam"][same]).reshape(ns, -1).max(1))) < 1e-6, N
+        assert np.max(np.abs(g["cost"] - ref["cost"]) / np.abs(ref["cost"])) < 1e-6, N
+        bad = []
+        for i in range(B):
+            r = kkt.kkt_residual(g["x"][i], g["u"][i], g["lam"][i], sb["ini"][i], sb["goal"][i], p[i], q[i], t[i])
+            if not (r["primal"] <= 5e-7 and r["dual"] <= 1e-4 * r["s_d"] and r["compl"] <= 1e-6):
+                bad.append((i, r))
+        assert not bad, (N, bad)
+    print(f"same iteration path {n_same}/{n_kept} (rounding yardstick {n_yard}/{n_kept})")
+    assert n_kept >= 0.9 * 48, n_kept
+    assert n_same >= n_yard - 0.02 * n_kept, f"iteration paths differ on {n_kept - n_same} of {n_kept}; yardstick {n_yard}"
 
 
 def test_dropin_run_quad_and_ocsys(eng, batch):
