@@ -355,6 +355,17 @@ __device__ inline double uniform(double v)
 // ipm_kernel 568 -> 551 ms at B = 4096, identical iteration counts).
 __device__ inline void sync() { asm volatile("" ::: "memory"); }
 __device__ inline void vm_sync() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// s_waitcnt operand that waits until at most n vector-memory operations are in flight and leaves the LDS / scalar
+// and export counters open (gfx9 encoding: vmcnt in bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8)
+__host__ __device__ constexpr int waitcnt_vm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
+static_assert(waitcnt_vm(45) == 0x8F7D && waitcnt_vm(63) == 0xCF7F, "vmcnt 45 = 0b10'1101, 63 = all ones");
+// the count for a chain step's coefficients: its fetch went out pf - 1 fetches (of fl loads) ago, and `steps` steps
+// (at most pf - 1 count) with st stores each were taken since; the 6-bit counter caps it
+__host__ __device__ constexpr int chain_vm(int pf, int fl, int st, int steps)
+{
+    const int n = (pf - 1) * fl + st * (steps < pf - 1 ? steps : pf - 1);
+    return n < 63 ? n : 63;
+}
 // the lane index behind an empty asm: the sweeps inlined into linear_solve derive their per-lane index tables
 // from it, and the asm keeps the compiler from hoisting those tables out of the sweep loop (live across every
 // other sweep they would cost registers the 256-register budget does not have)

@@ -53,6 +53,24 @@ __device__ inline void bst(double v, Rsrc r, unsigned voff, int soff)
 {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32, v), r, voff, soff, 0);
 }
+// the workspace as a wave-uniform byte pointer (readfirstlane of both halves, as uniform() for doubles): a load
+// from it plus a 32-bit per-lane byte offset is the SGPR-base form of global_load, whose stage stepping is
+// scalar (the ws argument of the non-inlined linear_solve arrives in VGPRs: every address formed from it is
+// 64-bit vector arithmetic per load)
+typedef __attribute__((address_space(1))) char gchar;
+__device__ inline const gchar *ws_uniform(const gdouble *p)
+{
+    const long long v = (long long)(const double *)p;
+    const int lo = __builtin_amdgcn_readfirstlane((int)v), hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return (const gchar *)(((long long)hi << 32) | (unsigned)lo);
+}
+// (the offset is made opaque at the load: hoisted out of a loop, its zero extension reaches instruction selection
+// as a 64-bit register and the load falls back to a 64-bit vector address)
+__device__ inline double gld(const gchar *base, unsigned &voff)
+{
+    asm volatile("" : "+v"(voff));
+    return *(const gdouble *)(base + voff);
+}
 
 
 // P_k store (WS_PST): stage-major [slot][PSTR], 16-byte aligned, so that the stage-parallel readers (refinement
@@ -807,7 +825,6 @@ __device__ __attribute__((always_inline)) inline void forward_chain(const Model 
     WS_TRAJ(ws);
     const int lane = opaque_lane();
     const int N = C.N;
-    const gdouble *tab = ws + WS_TAB, *rec = ws + WS_REC;
     const int a1 = lane >> 4, j1 = lane & 15;
     const double m16 = (j1 == 0) ? 1.0 : 0.0;
     const int h = lane & 1, o = min(lane >> 1, NA - 1), oi = min(o, NX - 1);
@@ -835,31 +852,67 @@ __device__ __attribute__((always_inline)) inline void forward_chain(const Model 
     const double ur = (h == 1 && o >= NX) ? 1.0 : 0.0;
     const double tw0 = -tcy + tcz + ((o == 13) ? ur : 0.0), tw1 = -tcx - tcz + ((o == 14) ? ur : 0.0);
     const double tw2 = tcy + tcz + ((o == 15) ? ur : 0.0), tw3 = tcx - tcz + ((o == 16) ? ur : 0.0);
-    const gdouble *kbase = fac ? rec + RC_KF + a1 : ws + WS_KREF + a1 * SX;
-    const int kstr = fac ? REC : 1;
-    const gdouble *cbase = fac ? tab + TB_c + oi : ws + WS_RC + oi * SX;
-    const int cstr = fac ? TB_W : 1;
     const int dof = o * SX + (o < NX ? 1 : 0);   // dx_{s+1}[o] or du_s[o - 13] (WS_DU follows WS_DX)
     if (lane < NA) S.ring[lane] = 0.0;           // x~_0 = 0
     if (lane < NX) DX[lane * SX] = 0.0;
     sync();
-    constexpr int PF = 6;   // with backward_chain's 5; measured 4 / 3 ... 7 / 6: profiles/r05_ab_prefetch.log, r05_ab_retune_final_flags.log
+    // with backward_chain's 4.  An even PF keeps the ring slot (s & 1) a constant of each unrolled step: 5 and 7
+    // measured +1.2 % kernel time against 4 and 6, which were equal (profiles/chain_ab_parts.log; round 5's
+    // prefetch scan: profiles/r05_ab_prefetch.log, r05_ab_retune_final_flags.log)
+    constexpr int PF = 6;
+    static_assert(PF % 2 == 0, "ring slot of a step fixed by its place in the body");
     double fK0[PF], fK1[PF], fkf[PF], fa[PF][4], fbv[PF], fc[PF];
-    auto fetch = [&](int s, double &K0, double &K1, double &kf, double *a4, double &bv, double &c) {
-        s = min(s, N - 1);
-        const gdouble *rs = rec + (size_t)s * REC, *ts = tab + (size_t)s * TB_W;
-        K0 = rs[RC_K + j1 * NU + a1];
-        K1 = rs[RC_K + 16 * NU + a1];
-        kf = kbase[(size_t)s * kstr];
+    // coefficient loads from the wave-uniform workspace base (SGPR pair) plus a 32-bit per-lane byte offset: the nine
+    // offsets are fixed for the sweep (opaque, so that they stay nine registers) and the stage is scalar state.  The
+    // record and the table row advance once per unrolled body, the fetches inside it reach their stage by a
+    // constant (the load's immediate: the table's base stands FB stages ahead to keep it within +-4 KB); the
+    // feed-forward and c, whose strides differ between the solve and a refinement sweep, advance by a scalar add
+    // per fetch.  The pointers are opaque where they advance: otherwise base + lane offset is hoisted as nine 64-bit
+    // vector invariants and every load adds the stage to one of them.  The fetches run PF - 1 stages ahead and past
+    // stage N - 1 without a clamp: what they read there stays inside the instance's workspace and is never used.
+    constexpr int FL = 9;   // loads per fetch
+    constexpr int FB = 3;
+    static_assert(WS_REC + (MAXN + PF) * REC <= WS_END && WS_TAB + (MAXN + PF) * TB_W <= WS_END &&
+                      WS_KREF + NU * SX + PF <= WS_END && WS_RC + NX * SX + PF <= WS_END,
+                  "forward_chain fetches up to PF - 1 stages past the horizon");
+    static_assert((PF - 1) * REC * 8 < 4096 && (PF - 1 - FB) * TB_W * 8 < 4096 && FB * TB_W * 8 <= 4096,
+                  "stage constants of a body within the load's immediate");
+    const gchar *ub = ws_uniform(ws);
+    unsigned oK0 = (unsigned)(WS_REC + RC_K + j1 * NU + a1) * 8u, oK1 = (unsigned)(WS_REC + RC_K + 16 * NU + a1) * 8u;
+    unsigned okf = (unsigned)(fac ? WS_REC + RC_KF + a1 : WS_KREF + a1 * SX) * 8u;
+    unsigned oa[4], obv = (unsigned)(WS_TAB + bvoff) * 8u;
+    unsigned oc = (unsigned)(fac ? WS_TAB + TB_c + oi : WS_RC + oi * SX) * 8u;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) a4[t] = ts[ac[t].off];
-        bv = ts[bvoff];
-        c = cbase[(size_t)s * cstr];
+    for (int t = 0; t < 4; ++t) {
+        oa[t] = (unsigned)(WS_TAB + ac[t].off) * 8u;
+        asm volatile("" : "+v"(oa[t]));
+    }
+    asm volatile("" : "+v"(oK0), "+v"(oK1), "+v"(okf), "+v"(obv), "+v"(oc));
+    const int kstr8 = uni(fac ? REC * 8 : 8), cstr8 = uni(fac ? TB_W * 8 : 8);
+    const gchar *sRec = ub, *sTab = ub + FB * TB_W * 8, *sKf = ub, *sC = ub;
+    // q: the stage relative to the body's first
+    auto fetch = [&](int q, double &K0, double &K1, double &kf, double *a4, double &bv, double &c) {
+        const gchar *r = sRec + q * REC * 8, *t4 = sTab + (q - FB) * TB_W * 8;
+        K0 = gld(r, oK0);
+        K1 = gld(r, oK1);
+        kf = gld(sKf, okf);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) a4[t] = gld(t4, oa[t]);
+        bv = gld(t4, obv);
+        c = gld(sC, oc);
+        sKf += kstr8;
+        sC += cstr8;
+        asm volatile("" : "+s"(sKf), "+s"(sC));
+    };
+    auto advance = [&](int n) {
+        sRec += n * REC * 8;
+        sTab += n * TB_W * 8;
+        asm volatile("" : "+s"(sRec), "+s"(sTab));
     };
     // the next coefficient fetch is issued right after this step's ring reads, into the slot the previous step
     // consumed (prefetch distance PF - 1 stages), so that its ~9 global loads issue under the ring reads' LDS
     // latency instead of between the step's result and its ring store (the chain's critical path)
-    auto step = [&](int s, double &K0, double &K1, double &kf, double *a4, double &bv, double &c,
+    auto step = [&](int q, int s, double &K0, double &K1, double &kf, double *a4, double &bv, double &c,
                     double &pK0, double &pK1, double &pkf, double *pa4, double &pbv, double &pc) {
         const double *xr = S.ring + (s & 1) * RING;
         // every LDS read of the step first: one wait, then the two independent halves of the step
@@ -868,7 +921,11 @@ __device__ __attribute__((always_inline)) inline void forward_chain(const Model 
 #pragma unroll
         for (int t = 0; t < 4; ++t) xa[t] = xr[acol[t]];
         __builtin_amdgcn_sched_barrier(0);
-        fetch(s + PF - 1, pK0, pK1, pkf, pa4, pbv, pc);
+        fetch(q, pK0, pK1, pkf, pa4, pbv, pc);
+        // one counted wait for the step's nine coefficients: loads return in order and the PF - 1 fetches issued
+        // after theirs may stay in flight (the chain has no global stores; every step issues a fetch).  The
+        // compiler's own waits stay in force behind it and add nothing while the count is right.
+        __builtin_amdgcn_s_waitcnt(waitcnt_vm(chain_vm(PF, FL, 0, 0)));
         __builtin_amdgcn_sched_barrier(0);
         double y = K0 * xj;
         y = fma(K1 * m16, x16, y);
@@ -889,16 +946,21 @@ __device__ __attribute__((always_inline)) inline void forward_chain(const Model 
         sync();
     };
 #pragma unroll
-    for (int q = 0; q < PF - 1; ++q) fetch(q, fK0[q], fK1[q], fkf[q], fa[q], fbv[q], fc[q]);
+    for (int q = 0; q < PF - 1; ++q) {
+        fetch(q, fK0[q], fK1[q], fkf[q], fa[q], fbv[q], fc[q]);
+        __builtin_amdgcn_sched_barrier(0);   // fetch by fetch, the order the steps' counted waits assume
+    }
+    advance(PF - 1);
 #define FSLOT(q) fK0[q], fK1[q], fkf[q], fa[q], fbv[q], fc[q]
     int s = 0;
     for (; s + PF <= N; s += PF) {   // straight-line body, step slot = s % PF, fetch slot = (s - 1) % PF
 #pragma unroll
-        for (int q = 0; q < PF; ++q) step(s + q, FSLOT(q), FSLOT((q + PF - 1) % PF));
+        for (int q = 0; q < PF; ++q) step(q, s + q, FSLOT(q), FSLOT((q + PF - 1) % PF));
+        advance(PF);
     }
 #pragma unroll
     for (int q = 0; q < PF - 1; ++q)
-        if (s + q < N) step(s + q, FSLOT(q), FSLOT((q + PF - 1) % PF));
+        if (s + q < N) step(q, s + q, FSLOT(q), FSLOT((q + PF - 1) % PF));
 #undef FSLOT
     vm_sync();   // the step goes to other lanes' stage-parallel passes through HBM
 }
@@ -1022,31 +1084,56 @@ __device__ __attribute__((always_inline)) inline void backward_chain(const Model
     const int gsl = min(lane, NU - 1);   // g_s entry this lane stores
     if (st) {
         const double v = xcol * rq[jc * SX + N] + pcv[N * 18 + j];   // ph_N = rq_N + P_N c~_{N-1}
-        S.ring[(N & 1) * RING + j] = v;
+        S.ring[j] = v;   // ring slot 0: the slots alternate with the steps taken, not with s
         ws[WS_PVK + (size_t)N * 18 + j] = v;
     }
     sync();
-    constexpr int PF = 5;   // see forward_chain's PF (4: -0.3 %, 6: -3.3 % with the final build flags)
+    // see forward_chain's PF: even, so that the ring slot is a constant of each unrolled step (with 5, the slot's
+    // address arithmetic was 14 VALU instructions of the step); 4 and 6 measured equal (profiles/chain_ab_parts.log)
+    constexpr int PF = 4;
     double fa[PF][4], fbv[PF][3], frr[PF][NU], fq[PF], fp[PF], fk[PF][NU];
-    // coefficient loads through a buffer resource: per-lane constant offsets, the stage's offsets in SGPRs (global
-    // loads needed a 64-bit address per load and stage; +0.3 % with the final build flags, the same in forward_chain
-    // measured slower: profiles/r05_ab_chain_buffer_loads.log, r05_ab_retest_final_flags.log)
+    // coefficient loads and the step's stores through a buffer resource: per-lane constant offsets, the stage's
+    // offsets in SGPRs (global loads needed a 64-bit address per load and stage; +0.3 % with the final build flags:
+    // profiles/r05_ab_chain_buffer_loads.log, r05_ab_retest_final_flags.log; forward_chain takes the SGPR-base form)
     const Rsrc wr = ws_rsrc(ws, WS_SIZE * 8);
-    auto fetch = [&](int s, double *a4, double *bv3, double *r4, double &q1, double &p1, double *k4) {
-        s = max(s, 0);
-        const int st = uni(s * TB_W * 8), s1 = uni(s * 8);
+    constexpr int FL = 14, ST = 2;   // vector-memory operations of a step: loads of its fetch, its global stores
+    // the stage as four scalar byte offsets (table row, [a][s] rows, 18-wide rows, record) that a fetch steps down;
+    // they stand PF - 1 stages above the fetched stage, which is the stage a step stores while it fetches, so the
+    // step's two stores take the same offsets and the loads carry the distance in their per-lane constants.  Below
+    // stage 0 a fetch reads inside the workspace what no step uses; only rq, at the workspace's start, is clamped.
+    constexpr int D = PF - 1;
+    static_assert(WS_TAB >= D * TB_W && WS_RR >= D && WS_PC >= D * 18 && WS_REC >= D * REC && WS_RQ == 0,
+                  "backward_chain fetches down to stage -(PF - 1)");
+    int oT = uni((N - 1 + D) * TB_W * 8), o1 = uni((N - 1 + D) * 8), oP = uni((N - 1 + D) * 18 * 8);
+    int oR = uni((N - 1 + D) * REC * 8);
+    unsigned va[4], vq = (unsigned)(WS_RQ + jc * SX) * 8u, vp = (unsigned)(WS_PC + j - D * 18) * 8u;
+    unsigned vk = (unsigned)(WS_REC + RC_K + j * NU - D * REC) * 8u;
+    unsigned vpv = (unsigned)(WS_PVK + j) * 8u, vgs = (unsigned)(WS_GS + gsl * SX) * 8u;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) a4[t] = bld(wr, (unsigned)(WS_TAB + ac[t].off) * 8u, st);
+    for (int t = 0; t < 4; ++t) {
+        va[t] = (unsigned)(WS_TAB + ac[t].off - D * TB_W) * 8u;
+        asm volatile("" : "+v"(va[t]));
+    }
+    asm volatile("" : "+v"(vq), "+v"(vp), "+v"(vk), "+v"(vpv), "+v"(vgs));
+    auto fetch = [&](int, double *a4, double *bv3, double *r4, double &q1, double &p1, double *k4) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) bv3[i] = bld(wr, (unsigned)(WS_TAB + TB_G + BV_SLOT + i) * 8u, st);
+        for (int t = 0; t < 4; ++t) a4[t] = bld(wr, va[t], oT);
 #pragma unroll
-        for (int a = 0; a < NU; ++a) r4[a] = bld(wr, (unsigned)(WS_RR + a * SX) * 8u, s1);
-        q1 = bld(wr, (unsigned)(WS_RQ + jc * SX) * 8u, s1);
-        p1 = bld(wr, (unsigned)(WS_PC + j) * 8u, uni(s * 18 * 8));
-        const int sr = uni(s * REC * 8);
-        const dvec2 k01 = bld2(wr, (unsigned)(WS_REC + RC_K + j * NU) * 8u, sr);
-        const dvec2 k23 = bld2(wr, (unsigned)(WS_REC + RC_K + j * NU + 2) * 8u, sr);
+        for (int i = 0; i < 3; ++i) bv3[i] = bld(wr, (unsigned)(WS_TAB + TB_G + BV_SLOT + i - D * TB_W) * 8u, oT);
+        static_assert((WS_TAB + TB_G + BV_SLOT) % 2 == 0 && TB_W % 2 == 0, "the compiler joins bv3[0], bv3[1]: FL counts one");
+#pragma unroll
+        for (int a = 0; a < NU; ++a) r4[a] = bld(wr, (unsigned)(WS_RR + a * SX - D) * 8u, o1);
+        q1 = bld(wr, vq, max(o1 - D * 8, 0));
+        p1 = bld(wr, vp, oP);
+        const dvec2 k01 = bld2(wr, vk, oR);
+        const dvec2 k23 = bld2(wr, vk + 16u, oR);
         k4[0] = k01.x; k4[1] = k01.y; k4[2] = k23.x; k4[3] = k23.y;
+    };
+    auto step_down = [&]() {
+        oT -= TB_W * 8;
+        o1 -= 8;
+        oP -= 18 * 8;
+        oR -= REC * 8;
     };
     // stage gradient g_s = B~_s^T ph_{s+1} + rr_s (model.hpp Bt_times order), identical in every lane
     auto grad = [&](const double *xr, const double *bv3, const double *r4, double *g) {
@@ -1057,11 +1144,14 @@ __device__ __attribute__((always_inline)) inline void backward_chain(const Model
         g[2] = (v + ey + ez) + xr[NX + 2] + r4[2];
         g[3] = (v + ex - ez) + xr[NX + 3] + r4[3];
     };
-    // as forward_chain: the fetch (15 global loads) goes out under the ring reads' LDS latency, into the slot
+    // as forward_chain: the fetch (14 buffer loads) goes out under the ring reads' LDS latency, into the slot
     // the previous step consumed (distance PF - 1)
-    auto step = [&](int s, double *a4, double *bv3, double *r4, double &q1, double &p1, double *k4,
+    auto step = [&](int q, int s, double *a4, double *bv3, double *r4, double &q1, double &p1, double *k4,
                     double *pa4, double *pbv3, double *pr4, double &pq1, double &pp1, double *pk4) {
-        const double *xr = S.ring + ((s + 1) & 1) * RING;
+        // ring slot of ph_{s+1}: the parity of the steps taken, which an even PF makes the parity of q (an odd one
+        // works and pays the slot's address arithmetic in every step)
+        const int par = (PF % 2 == 0) ? (q & 1) : ((N - 1 - s) & 1);
+        const double *xr = S.ring + par * RING;
         double xa[4], xg[NA];
 #pragma unroll
         for (int t = 0; t < 4; ++t) xa[t] = xr[crow[t]];
@@ -1069,6 +1159,16 @@ __device__ __attribute__((always_inline)) inline void backward_chain(const Model
         for (int i = 3; i < NA; ++i) xg[i] = xr[i];
         __builtin_amdgcn_sched_barrier(0);
         fetch(s - PF + 1, pa4, pbv3, pr4, pq1, pp1, pk4);
+        // one counted wait for the step's coefficients.  Operations return in order; behind this step's fetch
+        // stand PF - 1 later fetches and the stores of the steps taken since (at most PF - 1 of them; the chain's
+        // t-th step has taken t, and slot q of the unrolled body is never earlier than the q-th), and the counter
+        // holds 63 at the most: a smaller count than the true one only waits for more.  The compiler's own waits
+        // stay in force behind it and add nothing while the count is right.
+        if (q == 0) __builtin_amdgcn_s_waitcnt(waitcnt_vm(chain_vm(PF, FL, ST, 0)));
+        else if (q == 1) __builtin_amdgcn_s_waitcnt(waitcnt_vm(chain_vm(PF, FL, ST, 1)));
+        else if (q == 2) __builtin_amdgcn_s_waitcnt(waitcnt_vm(chain_vm(PF, FL, ST, 2)));
+        else if (q == 3) __builtin_amdgcn_s_waitcnt(waitcnt_vm(chain_vm(PF, FL, ST, 3)));
+        else __builtin_amdgcn_s_waitcnt(waitcnt_vm(chain_vm(PF, FL, ST, PF - 1)));
         __builtin_amdgcn_sched_barrier(0);
         double acc = 0.0;
 #pragma unroll
@@ -1086,22 +1186,27 @@ __device__ __attribute__((always_inline)) inline void backward_chain(const Model
         gl = (gsl == 3) ? g[3] : gl;
         // unconditional (identical values to identical addresses: both halves of column j after pair_sum, lanes
         // past 2 NA with j clamped to 16, lanes >= NU with the g index clamped to NU - 1)
-        S.ring[(s & 1) * RING + j] = acc;
-        ws[WS_PVK + (size_t)s * 18 + j] = acc;   // ph_s for the costate identity
-        gs[gsl * SX + s] = gl;
+        S.ring[(par ^ 1) * RING + j] = acc;
+        bst(acc, wr, vpv, oP);   // ph_s for the costate identity
+        bst(gl, wr, vgs, o1);    // g_s
+        step_down();
         sync();
     };
 #define BSLOT(q) fa[q], fbv[q], frr[q], fq[q], fp[q], fk[q]
 #pragma unroll
-    for (int q = 0; q < PF - 1; ++q) fetch(N - 1 - q, BSLOT(q));
+    for (int q = 0; q < PF - 1; ++q) {
+        fetch(N - 1 - q, BSLOT(q));   // (the stage is in the scalar offsets; the argument names it)
+        step_down();
+        __builtin_amdgcn_sched_barrier(0);   // fetch by fetch, the order the steps' counted waits assume
+    }
     int s = N - 1;
     for (; s - PF >= -1; s -= PF) {   // steps s .. s - PF + 1, slot (N - 1 - s) % PF, fetch slot one behind
 #pragma unroll
-        for (int q = 0; q < PF; ++q) step(s - q, BSLOT(q), BSLOT((q + PF - 1) % PF));
+        for (int q = 0; q < PF; ++q) step(q, s - q, BSLOT(q), BSLOT((q + PF - 1) % PF));
     }
 #pragma unroll
     for (int q = 0; q < PF - 1; ++q)
-        if (s - q >= 0) step(s - q, BSLOT(q), BSLOT((q + PF - 1) % PF));
+        if (s - q >= 0) step(q, s - q, BSLOT(q), BSLOT((q + PF - 1) % PF));
 #undef BSLOT
     vm_sync();
     // (2) k_ref_k = -Quu_k^{-1} g_k (lane = k)
