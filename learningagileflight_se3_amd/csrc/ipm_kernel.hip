@@ -61,6 +61,7 @@ constexpr int WS_RC = WS_RR + NU * SX;           // [i][k]       (dynamics rows)
 constexpr int WS_BDX = WS_RC + NX * SX;          // refinement backups
 constexpr int WS_BDU = WS_BDX + NX * SX;
 constexpr int WS_BLP = WS_BDU + NU * SX;
+constexpr int BK_DX = 0, BK_DU = WS_BDU - WS_BDX, BK_LP = WS_BLP - WS_BDX;   // the backup from its base WS_BDX
 constexpr int WS_TAB = WS_BLP + NX * SX;         // [k][TB_W] stage table (riccati_tables.hpp)
 constexpr int PSTR = NUP17 + 1;    // P_k store stride: every stage 16-byte aligned
 constexpr int WS_PST = WS_TAB + MAXN * TB_W;     // [k][PSTR] P_{k+1} (packed upper): refinement P c~, costates
@@ -750,52 +751,57 @@ __device__ __noinline__ int fac_check(const Model &M, const Attitude &at, Smem &
 #endif
 
 // ---- linear solves of the Newton system --------------------------------------------------------------
-// One non-inlined function holds every sweep of a Newton-system solve, each inlined exactly once in one loop:
+// One non-inlined function holds every sweep of a Newton-system solve, each inlined exactly once in one loop (the
+// costates pass twice: the solve's and the refinement step's):
 //   factor:  build_table + backward_full (factorisation) then forward_chain; otherwise the right-hand side
 //            (rq, rr, rc) already in the workspace goes through backward_chain + forward_chain.  factor = 2:
 //            an inertia-correction retry (other delta_w, same iterate): the stage table, which does not hold
 //            delta_w, is reused (72 % of IPM iterations retry at least once)
 //   refine:  IPOPT's iterative refinement (min 1, max 10 steps; stop at residual ratio <= 1e-10 or when the
 //            ratio stops improving): kkt_residual, back up the solution, one chain sweep on the residual,
-//            add, kkt_residual again (PDFullSpaceSolver::Solve)
-// the refinement's solution backup (HBM) added to (ADD) or copied over the step dx, lam+, du (LDS), four strided
-// elements per lane in flight at a time: the one-element loop waited for every load, 15 dependent round trips to
-// L2 / MALL per refinement step, 4 now.  (All 26 loads at once held 52 more registers across linear_solve and doubled
-// ipm_kernel's spills around the call; chunks of 2 / 3 / 6 measured slower than 4: profiles/r05_ab_backup_chunks*.log)
-template <bool ADD>
-__device__ __attribute__((always_inline)) inline void apply_backup(double *DX, double *LP, double *DU, const gdouble *bdx,
-                                                                   const gdouble *blp, const gdouble *bdu)
+//            add, kkt_residual again; a step that does not lower the ratio is reverted (PDFullSpaceSolver::Solve)
+// A refinement step copies the solution dx, lam+, du (LDS) to the backup in the HBM workspace with a strided loop
+// whose stores drain under the sweep that follows; the sweep writes its correction over dx, du, lam+; and
+// costates_identity<true>, the sweep's last pass, in which lane l already reads dx of stage l + 1 and du of stage l
+// and writes lam+ of stage l, loads the backup of exactly those elements under its P_k stream and writes backup +
+// correction back.  There is no pass of its own for the add (it was one: four chunks of strided loads, each waited
+// for, 2.1 % of instance cycles: profiles/refine_fold_timers.log).  Taking the backup from the registers of
+// kkt_residual or of the costates pass instead of the loop measured slower: those stores stand right before the
+// pass's closing wait.
+// the revert (rare): the backup copied over the elements a refinement step changes, dx of stages 0..N, lam+ and du of
+// stages 0..N-1, lane = stage.  Four rows per lane in flight at a time: all 30 loads at once held 52 more registers
+// across linear_solve and doubled ipm_kernel's spills around the call (profiles/r05_ab_backup_chunks*.log).
+__device__ __attribute__((always_inline)) inline void revert_to_backup(double *DX, double *LP, double *DU,
+                                                                       const gdouble *bk, int N)
 {
     const int lane = lane_id();
+    if (lane > N) return;
+    const bool in = lane < N;
     constexpr int CH = 4;
 #pragma unroll 1
-    for (int e0 = 0; e0 < NX * SX; e0 += CH * WAVE) {
+    for (int i0 = 0; i0 < NX; i0 += CH) {
         double vx[CH], vl[CH];
 #pragma unroll
         for (int i = 0; i < CH; ++i) {
-            const int e = min(e0 + i * WAVE + lane, NX * SX - 1);
-            vx[i] = bdx[e];
-            vl[i] = blp[e];
+            const int e = min(i0 + i, NX - 1) * SX + lane;
+            vx[i] = bk[BK_DX + e];
+            vl[i] = bk[BK_LP + e];
         }
 #pragma unroll
         for (int i = 0; i < CH; ++i) {
-            const int e = e0 + i * WAVE + lane;
-            if (e < NX * SX) {
-                DX[e] = ADD ? vx[i] + DX[e] : vx[i];
-                LP[e] = ADD ? vl[i] + LP[e] : vl[i];
+            const int e = (i0 + i) * SX + lane;
+            if (i0 + i < NX) {
+                DX[e] = vx[i];
+                if (in) LP[e] = vl[i];
             }
         }
     }
-#pragma unroll 1
-    for (int e0 = 0; e0 < NU * SX; e0 += CH * WAVE) {
-        double vu[CH];
+    if (in) {
+        double vu[NU];
 #pragma unroll
-        for (int i = 0; i < CH; ++i) vu[i] = bdu[min(e0 + i * WAVE + lane, NU * SX - 1)];
+        for (int a = 0; a < NU; ++a) vu[a] = bk[BK_DU + a * SX + lane];
 #pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int e = e0 + i * WAVE + lane;
-            if (e < NU * SX) DU[e] = ADD ? vu[i] + DU[e] : vu[i];
-        }
+        for (int a = 0; a < NU; ++a) DU[a * SX + lane] = vu[a];
     }
 }
 
@@ -807,19 +813,19 @@ __device__ __noinline__ int linear_solve(const Model &M, const Attitude &at, Sme
                                          double *dump_pre)
 {
     WS_TRAJ(ws);
-    gdouble *bdx = ws + WS_BDX, *bdu = ws + WS_BDU, *blp = ws + WS_BLP;
+    gdouble *bk = ws + WS_BDX;
     double ratio = 0.0;
     // step -1 is the solve itself, steps 0..9 are refinement sweeps
     for (int step = -1; step < 10; ++step) {
-        const int lane = opaque_lane();
         if (step >= 0) {
             if (!refine || (step >= 1 && ratio <= 1e-10)) break;
             // back up the current solution (each lane its own slots)
+            const int lane = opaque_lane();
             for (int e = lane; e < NX * SX; e += WAVE) {
-                bdx[e] = DX[e];
-                blp[e] = LP[e];
+                bk[BK_DX + e] = DX[e];
+                bk[BK_LP + e] = LP[e];
             }
-            for (int e = lane; e < NU * SX; e += WAVE) bdu[e] = DU[e];
+            for (int e = lane; e < NU * SX; e += WAVE) bk[BK_DU + e] = DU[e];
         }
         const int fac = (step < 0) && factor;
         PT_BEGIN(S);
@@ -844,15 +850,12 @@ __device__ __noinline__ int linear_solve(const Model &M, const Attitude &at, Sme
         }
         for (int r = 0; r < 1; ++r) forward_chain(M, S, C, ws, fac);
         PT_END(S, 4);
-        for (int r = 0; r < 1; ++r) costates_identity(S, C, ws, fac);
+        // a refinement sweep (step >= 0; never a factorisation) adds the solution it started from
+        if (step >= 0) costates_identity<true>(S, C, ws, 0, bk);
+        else costates_identity<false>(S, C, ws, fac, nullptr);
         PT_END(S, 5);
         sweeps++;
-        if (step >= 0) {
-            apply_backup<true>(DX, LP, DU, bdx, blp, bdu);
-            vm_sync();
-        } else if (dump_pre) {
-            dump_step(S, ws, C.N, dump_pre);
-        }
+        if (step < 0 && dump_pre) dump_step(S, ws, C.N, dump_pre);
         PT_END(S, 11);
         if (!refine) break;
         double nr = 0.0;
@@ -866,7 +869,7 @@ __device__ __noinline__ int linear_solve(const Model &M, const Attitude &at, Sme
         if (step < 2) ratios[1 + step] = nr;
         ratios[3] += 1;
         if (!(nr < ratio)) {
-            apply_backup<false>(DX, LP, DU, bdx, blp, bdu);
+            revert_to_backup(DX, LP, DU, bk, C.N);
             vm_sync();
             break;
         }

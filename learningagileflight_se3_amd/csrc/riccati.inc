@@ -974,8 +974,10 @@ __device__ __attribute__((always_inline)) inline void forward_chain(const Model 
 #ifndef LAFSE3_PB
 #define LAFSE3_PB 24
 #endif
-template <typename F>
-__device__ __attribute__((always_inline)) inline void p_rows_stream(const gdvec2 *pp2, F &&f)
+// issued(): called once, after the last block's loads are issued and before their first use: a caller's own loads
+// placed there return behind the stream's and wait under the last block's arithmetic.
+template <typename F, typename G>
+__device__ __attribute__((always_inline)) inline void p_rows_stream(const gdvec2 *pp2, F &&f, G &&issued)
 {
     constexpr int NE = up17(NX - 1, NA - 1) + 1;   // entries of rows 0..12
     constexpr int NP = (NE + 1) / 2;               // 16-byte pieces
@@ -986,6 +988,7 @@ __device__ __attribute__((always_inline)) inline void p_rows_stream(const gdvec2
 #pragma unroll
         for (int i = 0; i < PB; ++i)
             if (q0 + i < NP) buf[i] = pp2[q0 + i];
+        if (q0 + PB >= NP) issued();
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int a = 0; a < NX; ++a)
@@ -998,12 +1001,29 @@ __device__ __attribute__((always_inline)) inline void p_rows_stream(const gdvec2
     }
 }
 
+template <typename F>
+__device__ __attribute__((always_inline)) inline void p_rows_stream(const gdvec2 *pp2, F &&f)
+{
+    p_rows_stream(pp2, f, [] {});
+}
+
 // ---- costates by the Riccati identity (stage-parallel, lane = k - 1) ------------------------------------------
 // lam+_{k-1} = (P_k dx~_k + p_k)[x rows] after a factorisation (p_k from [F], p_N = h~ terminal gradient), and
 // lam+_{k-1} = (P_k (dx~_k - c~_{k-1}) + ph_k)[x rows] after a refinement sweep (ph_k = p_k + P_k c~_{k-1} from
 // backward_chain, c~ = rc): the cost-to-go gradient at the new state, equal to the adjoint recursion's value
 // (the oracle's recursion) up to rounding.  dx~_k = [dx_k ; du_{k-1}].
-__device__ __attribute__((always_inline)) inline void costates_identity(Smem &S, const Ctl &C, gdouble *ws, int fac)
+// ADD: the instance that ends a refinement step (fac = 0) and also forms the refined solution.  dx, du and lam+ then
+// hold the sweep's correction, `add` is the backup set with the solution the sweep started from, and lane l writes
+// backup + correction over the elements of its own stage, the ones it reads and writes anyway: lam+ of stage l, dx of
+// stage l + 1, du of stage l.  dx of stage 0 is left as forward_chain wrote it: 0 in every correction and every
+// solution.  The 30 backup loads go out behind the last block of the P_k stream and return under its arithmetic; the
+// correction is read from LDS again (xt has c~ subtracted) before any sum is written, and no lane touches another
+// lane's elements.  A template parameter, not a run-time flag: with a wave-uniform branch around the loads inside the
+// stream, linear_solve took 240 accumulation registers instead of 114 and ipm_kernel's scratch operations around the
+// call went from 140 to 802.
+template <bool ADD>
+__device__ __attribute__((always_inline)) inline void costates_identity(Smem &S, const Ctl &C, gdouble *ws, int fac,
+                                                                        const gdouble *add)
 {
     WS_TRAJ(ws);
     const int lane = opaque_lane();
@@ -1017,22 +1037,47 @@ __device__ __attribute__((always_inline)) inline void costates_identity(Smem &S,
         for (int j = 0; j < NX; ++j) xt[j] = DX[j * SX + k];
 #pragma unroll
         for (int a = 0; a < NU; ++a) xt[NX + a] = DU[a * SX + k - 1];
-        if (!fac) {
+        if (ADD || !fac) {
 #pragma unroll
             for (int j = 0; j < NX; ++j) xt[j] -= rc[j * SX + k - 1];
         }
         const gdouble *pv = ws + WS_PVK + (size_t)k * 18;
-        const bool term = fac && k == N;   // p_N of a factorisation: the terminal gradient (u_prev part 0)
+        const bool term = !ADD && fac && k == N;   // p_N of a factorisation: the terminal gradient (u_prev part 0)
         double acc[NX];
 #pragma unroll
         for (int i = 0; i < NX; ++i) acc[i] = term ? (double)ws[WS_PN + i] : (double)pv[i];
+        double bx[NX], bu[NU], bl[NX];
         // row i's terms arrive in column order (P(a, i) for a < i, then row i): lam_i + sum_j P(i, j) xt_j
         p_rows_stream((const gdvec2 *)pp, [&](int a, int b, double P) {
             acc[a] = fma(P, xt[b], acc[a]);
             if (b != a && b < NX) acc[b] = fma(P, xt[a], acc[b]);
-        });
+        }, [&] {
+            if (ADD) {
 #pragma unroll
-        for (int i = 0; i < NX; ++i) LP[i * SX + k - 1] = acc[i];
+                for (int i = 0; i < NX; ++i) bl[i] = add[BK_LP + i * SX + k - 1];
+#pragma unroll
+                for (int j = 0; j < NX; ++j) bx[j] = add[BK_DX + j * SX + k];
+#pragma unroll
+                for (int a = 0; a < NU; ++a) bu[a] = add[BK_DU + a * SX + k - 1];
+            }
+        });
+        if (ADD) {
+            double cx[NX], cu[NU];
+#pragma unroll
+            for (int j = 0; j < NX; ++j) cx[j] = DX[j * SX + k];
+#pragma unroll
+            for (int a = 0; a < NU; ++a) cu[a] = DU[a * SX + k - 1];
+            sync();
+#pragma unroll
+            for (int i = 0; i < NX; ++i) LP[i * SX + k - 1] = bl[i] + acc[i];
+#pragma unroll
+            for (int j = 0; j < NX; ++j) DX[j * SX + k] = bx[j] + cx[j];
+#pragma unroll
+            for (int a = 0; a < NU; ++a) DU[a * SX + k - 1] = bu[a] + cu[a];
+        } else {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) LP[i * SX + k - 1] = acc[i];
+        }
     }
     vm_sync();
 }
