@@ -176,7 +176,12 @@ int lafse3_get_input(lafse3_ctx *ctx, int64_t B, const double *ini_state, const 
 /* Reward of given state trajectories x B x (N+1) x 13 (the scoring half of run_quad.objective,
  * quad_policy.py:78-91: rotor tips quad_model.py:239-276, obstacle.collis_det solid_geometry.py:104-168,
  * goal path term over rows N-4..N-1).  reward B.  Not a solver launch: the timing, counters and device error
- * word of the most recent solver launch (lafse3_last_kernel_ms / _last_counters / _check_device) are kept. */
+ * word of the most recent solver launch (lafse3_last_kernel_ms / _last_counters / _check_device) are kept.
+ * Short horizons: the path term indexes a numpy array of N+1 rows, so at N = 2 and 3 a negative row N-1-p wraps to
+ * row N-1-p + N+1 (N = 3: rows 2, 1, 0, 3; N = 2: rows 1, 0, 2, 1), as collis_det's t-1 already does.  At N = 1 the
+ * reference raises IndexError (row -3 of 2): lafse3_reward, lafse3_objective and lafse3_sol_gradient return
+ * LAFSE3_EINVAL there, before any allocation or launch.  The solves that score no reward (lafse3_ocp_solve, _f32,
+ * lafse3_ocp_sensitivity, lafse3_get_input) accept horizon 1. */
 int lafse3_reward(lafse3_ctx *ctx, int64_t B, const double *x, const double *goal, const double *gate12,
                   double *reward, void *stream);
 

@@ -143,6 +143,18 @@ static int check_call(const lafse3_ctx *c, int64_t B, std::initializer_list<cons
     return LAFSE3_OK;
 }
 
+// The reward's goal path term reads rows N-4..N-1 of the N+1 trajectory rows with numpy's wrap of negative rows
+// (quad_policy.py:88-89; ipm_kernel.hip reward_fused).  At horizon 1 the reference indexes row -3 of two rows and
+// raises: the entry points that score a reward refuse that horizon before any allocation or launch.
+static int check_reward_horizon(const lafse3_ctx *c, const char *entry)
+{
+    if (c->prm.horizon >= 2) return LAFSE3_OK;
+    char buf[256];
+    snprintf(buf, sizeof(buf), "%s: the reward is undefined at horizon %d: its goal path term reads row N-4 of the N+1 "
+             "trajectory rows, which the reference cannot index below horizon 2", entry, (int)c->prm.horizon);
+    return fail(LAFSE3_EINVAL, buf);
+}
+
 extern "C" {
 
 int lafse3_default_params(lafse3_params *p)
@@ -487,6 +499,7 @@ int lafse3_objective(lafse3_ctx *c, int64_t B, const double *ini, const double *
                      int32_t *status, void *stream)
 {
     if (const int rc = check_call(c, B, {ini, goal, gate12, p_tra, a_tra, t, reward})) return rc;
+    if (const int rc = check_reward_horizon(c, "lafse3_objective")) return rc;
     if (B == 0) return LAFSE3_OK;
     DeviceGuard dev(c->device);
     if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
@@ -503,6 +516,7 @@ int lafse3_sol_gradient(lafse3_ctx *c, int64_t B, const double *ini, const doubl
                         void *stream)
 {
     if (const int rc = check_call(c, B, {ini, goal, gate12, dnn_out, out8}, 9)) return rc;
+    if (const int rc = check_reward_horizon(c, "lafse3_sol_gradient")) return rc;
     const bool ift = c->prm.grad_mode == 1;
     if (ift && u_last) return fail(LAFSE3_EINVAL, "grad_mode 1 (IFT) linearises the nominal solve: u_last must be NULL");
     if (B == 0) return LAFSE3_OK;
@@ -556,6 +570,7 @@ int lafse3_reward(lafse3_ctx *c, int64_t B, const double *x, const double *goal,
                   void *stream)
 {
     if (const int rc = check_call(c, B, {x, goal, gate12, reward})) return rc;
+    if (const int rc = check_reward_horizon(c, "lafse3_reward")) return rc;
     if (B == 0) return LAFSE3_OK;
     DeviceGuard dev(c->device);
     if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);

@@ -1668,7 +1668,10 @@ __device__ __noinline__ double reward_fused(const lafse3_params &prm, Smem &S, i
     double path = 0.0;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const int t = N - 1 - p;
+        // rows N-1-p of the N+1 trajectory rows, negative rows wrapped as numpy wraps them (N = 2, 3;
+        // quad_policy.py:88-89).  N = 1 never gets here: the host refuses it (api.hip check_reward_horizon)
+        int t = N - 1 - p;
+        if (t < 0) t += N + 1;
         double d[3] = {S.x[0 * SX + t] - S.goal[0], S.x[1 * SX + t] - S.goal[1], S.x[2 * SX + t] - S.goal[2]};
         path += dot3(d, d);
     }

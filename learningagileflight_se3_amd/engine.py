@@ -347,7 +347,9 @@ class Engine:
         return (t, it) if want_iters else t
 
     def reward(self, x, goal, gate12):
-        """Score given trajectories (B, N+1, 13) as run_quad.objective does -> reward (B,)."""
+        """Score given trajectories (B, N+1, 13) as run_quad.objective does -> reward (B,).
+        Needs horizon >= 2, as objective and sol_gradient do: the goal path term reads rows N-4..N-1 with numpy's
+        wrap of negative rows, which the reference cannot index at horizon 1 (Lafse3Error there)."""
         d, f64 = self.device, torch.float64
         xs = _dev_tensor(x, (self.horizon + 1, NX), f64, d, "x")
         B = xs.shape[0]

@@ -2700,15 +2700,27 @@ static double line_vertical(const line_t *L, const double *pt)
     cross3(d, L->dir, c);
     return magni3(c);
 }
-static double line_distance(const line_t *L, const double *pt)
+/* line.distance(): solid_geometry.py:66-78.  *kind: LD_PERP when the perpendicular distance was returned,
+ * LD_END when the distance to an end point was */
+enum { LD_NONE = 0, LD_PERP = 1, LD_END = 2 };
+static double line_distance(const line_t *L, const double *pt, int *kind)
 {
     double a = line_vertical(L, pt);
     double d1[3] = {pt[0] - L->p1[0], pt[1] - L->p1[1], pt[2] - L->p1[2]};
     double d2[3] = {pt[0] - L->p2[0], pt[1] - L->p2[1], pt[2] - L->p2[2]};
     double d3[3] = {L->p1[0] - L->p2[0], L->p1[1] - L->p2[1], L->p1[2] - L->p2[2]};
     double b = magni3(d1), c = magni3(d2), d = magni3(d3);
-    if (b > c) return ((b * b - d * d) > a * a) ? c : a;
-    return ((c * c - d * d) > a * a) ? b : a;
+    int end;
+    double r;
+    if (b > c) {
+        end = (b * b - d * d) > a * a;
+        r = end ? c : a;
+    } else {
+        end = (c * c - d * d) > a * a;
+        r = end ? b : a;
+    }
+    *kind = end ? LD_END : LD_PERP;
+    return r;
 }
 
 /* obstacle(point1..4): solid_geometry.py:82-102 */
@@ -2724,21 +2736,29 @@ void orc_obstacle_init(obstacle_t *O, const double *g12)
 
 /* collis_det(vert_traj, horizon): solid_geometry.py:104-168.
  * branch: 0 = starts behind plane1 / never crosses; 1+4*p+b: last matching plane p, b=0 inside, 1 edge.
- * co: 1 if the crossing is inside the gate. */
-static double collis_det(const obstacle_t *O, const double *traj, int stride, int horizon, int *branch, int *co)
+ * co: 1 if the crossing is inside the gate.
+ * tcross (nullable): the first stage behind plane 1, CROSS_NEVER when there is none among stages 0..horizon-1,
+ * CROSS_BEHIND when stage 0 is behind already.  ldkind (nullable): for an edge branch, which outcome of
+ * line.distance gave the minimum over the three edge lines (the first of equal minima); LD_NONE otherwise. */
+enum { CROSS_NEVER = -1, CROSS_BEHIND = -2 };
+static double collis_det(const obstacle_t *O, const double *traj, int stride, int horizon, double dmin, int *branch,
+                         int *co, int *tcross, int *ldkind)
 {
     double collision = 0;
     *co = 0;
     *branch = 0;
+    if (tcross) *tcross = CROSS_BEHIND;
+    if (ldkind) *ldkind = LD_NONE;
     const double *n0 = O->pl[0].normal;
     double d0[3];
     for (int i = 0; i < 3; ++i) d0[i] = traj[i] - O->centroid[i];
     if (dot3(n0, d0) < 0) return 0;
-    const double dmin = 0.2;
+    if (tcross) *tcross = CROSS_NEVER;
     for (int t = 0; t < horizon; ++t) {
         const double *pt = traj + t * stride;
         double dd[3] = {pt[0] - O->centroid[0], pt[1] - O->centroid[1], pt[2] - O->centroid[2]};
         if (!(dot3(n0, dd) < 0)) continue;
+        if (tcross) *tcross = t;
         const double *pp = traj + ((t - 1 + (horizon + 1)) % (horizon + 1)) * stride; /* t-1, -1 wraps */
         /* interpoint (plane1): solid_geometry.py:43-47 */
         double dir[3], dv[3] = {pt[0] - pp[0], pt[1] - pp[1], pt[2] - pp[2]};
@@ -2758,14 +2778,20 @@ static double collis_det(const obstacle_t *O, const double *traj, int stride, in
                     collision = -(e * e);
                     *co = 1;
                     *branch = 1 + 4 * p;
+                    if (ldkind) *ldkind = LD_NONE;
                 } else {
                     /* edge lines: plane1 {4,1,2}, plane2 {1,2,3}, plane3 {2,3,4}, plane4 {3,4,1} */
                     int l0 = (p + 3) % 4, l1 = p, l2 = (p + 1) % 4;
-                    double m = line_distance(&O->ln[l0], X);
-                    m = fmin(m, line_distance(&O->ln[l1], X));
-                    m = fmin(m, line_distance(&O->ln[l2], X));
+                    int k0, k1, k2;
+                    double m0 = line_distance(&O->ln[l0], X, &k0);
+                    double m1 = line_distance(&O->ln[l1], X, &k1);
+                    double m2 = line_distance(&O->ln[l2], X, &k2);
+                    double m = m0;
+                    m = fmin(m, m1);
+                    m = fmin(m, m2);
                     collision = -2 * dmin * m - dmin * dmin;
                     *branch = 2 + 4 * p;
+                    if (ldkind) *ldkind = (m == m0) ? k0 : (m == m1) ? k1 : k2;
                 }
             }
         }
@@ -2775,8 +2801,11 @@ static double collis_det(const obstacle_t *O, const double *traj, int stride, in
 }
 
 /* rotor tips (quad_model.py:239-276) + reward (quad_policy.py:80-90) */
+/* detail (nullable): per rotor [crossing stage, line-distance outcome] of collis_det.
+ * The goal path term reads rows N-1-p, p = 0..3, of a numpy array of N+1 rows (quad_policy.py:88-89): a negative
+ * row (N = 2, 3) wraps to row + N+1.  N = 1 (row -3 of 2: IndexError in the reference) is refused by the callers. */
 static double reward_from_traj(const orc_params *P, const obstacle_t *O, const double *goal, const double *x,
-                               int N, int *branches)
+                               int N, int *branches, int *detail)
 {
     double a = P->wing_len * 0.5 / sqrt(2.0);
     double b[4][3] = {{a, a, 0}, {-a, a, 0}, {-a, -a, 0}, {a, -a, 0}};
@@ -2793,13 +2822,19 @@ static double reward_from_traj(const orc_params *P, const obstacle_t *O, const d
     }
     double col = 0;
     for (int r = 0; r < 4; ++r) {
-        int br, co;
-        col += collis_det(O, tr[r], 3, N, &br, &co);
+        int br, co, tc, lk;
+        col += collis_det(O, tr[r], 3, N, P->d_min, &br, &co, &tc, &lk);
         if (branches) branches[r] = br;
+        if (detail) {
+            detail[r * 2] = tc;
+            detail[r * 2 + 1] = lk;
+        }
     }
     double path = 0;
     for (int p = 0; p < 4; ++p) {
-        const double *xt = x + (N - 1 - p) * NX;
+        int row = N - 1 - p;
+        if (row < 0) row += N + 1;
+        const double *xt = x + row * NX;
         double d[3] = {xt[0] - goal[0], xt[1] - goal[1], xt[2] - goal[2]};
         path += dot3(d, d);
     }
@@ -2896,18 +2931,31 @@ int orc_solve_q(const orc_params *P, int64_t B, const double *ini, const double 
     return 0;
 }
 
-/* Reward of given state trajectories (B x (N+1) x 13) against gates (B x 12) and goals. */
-int orc_reward(const orc_params *P, int64_t B, const double *x, const double *goal, const double *gate12,
-               double *reward, int32_t *branches)
+/* Reward of given state trajectories (B x (N+1) x 13) against gates (B x 12) and goals.
+ * detail (nullable) B x 4 x 2 int32: per rotor, the crossing stage (the first stage behind plane 1; -1 never
+ * crosses, -2 starts behind) and, for an edge branch, the line-distance outcome behind the minimum
+ * (1 perpendicular, 2 end point; 0 for the other branches).
+ * Returns -1 and writes nothing at horizon 1 (and outside 2..NMAX): the reference's path term indexes row -3 of a
+ * two-row trajectory there, an IndexError. */
+int orc_reward_detail(const orc_params *P, int64_t B, const double *x, const double *goal, const double *gate12,
+                      double *reward, int32_t *branches, int32_t *detail)
 {
     const int N = P->horizon;
+    if (N < 2 || N > NMAX) return -1;
 #pragma omp parallel for schedule(static)
     for (int64_t b = 0; b < B; ++b) {
         obstacle_t O;
         orc_obstacle_init(&O, gate12 + b * 12);
-        reward[b] = reward_from_traj(P, &O, goal + b * 3, x + b * (N + 1) * NX, N, branches ? branches + b * 4 : NULL);
+        reward[b] = reward_from_traj(P, &O, goal + b * 3, x + b * (N + 1) * NX, N, branches ? branches + b * 4 : NULL,
+                                     detail ? detail + b * 8 : NULL);
     }
     return 0;
+}
+
+int orc_reward(const orc_params *P, int64_t B, const double *x, const double *goal, const double *gate12,
+               double *reward, int32_t *branches)
+{
+    return orc_reward_detail(P, B, x, goal, gate12, reward, branches, NULL);
 }
 
 /* collis_det on raw tracks (tests): tracks B x (horizon+1) x 3 */
@@ -2918,7 +2966,7 @@ int orc_collis_det(int64_t B, int horizon, const double *gate12, const double *t
         obstacle_t O;
         orc_obstacle_init(&O, gate12 + b * 12);
         int br, c;
-        out[b] = collis_det(&O, tracks + b * (horizon + 1) * 3, 3, horizon, &br, &c);
+        out[b] = collis_det(&O, tracks + b * (horizon + 1) * 3, 3, horizon, 0.2, &br, &c, NULL, NULL);
         if (branch) branch[b] = br;
         if (co) co[b] = c;
     }
@@ -3131,7 +3179,7 @@ static int orc_ift_probes(const orc_params *P, const orc_inst *I, orc_ws *W, con
         }
         double xp[(NMAX + 1) * NX];
         for (int e = 0; e < (N + 1) * NX; ++e) xp[e] = xs[e] + delta * W->dx[e];
-        Rprobe[q] = reward_from_traj(P, O, goal, xp, N, NULL);
+        Rprobe[q] = reward_from_traj(P, O, goal, xp, N, NULL, NULL);
     }
     return fac_ok;
 }
@@ -3147,6 +3195,7 @@ int orc_sol_gradient(const orc_params *P, int64_t B, const double *ini, const do
                      const float *dnn_out, const double *ulast, double *out8, double *rewards_out, int32_t *status)
 {
     const int N = P->horizon;
+    if (N < 2 || N > NMAX) return -1;   /* horizon 1: the reward is undefined (orc_reward_detail) */
     double *R = rewards_out ? rewards_out : (double *)malloc(sizeof(double) * 9 * (size_t)B);
 #pragma omp parallel for schedule(dynamic, 1)
     for (int64_t job = 0; job < B * 9; ++job) {
@@ -3172,7 +3221,7 @@ int orc_sol_gradient(const orc_params *P, int64_t B, const double *ini, const do
         int st = orc_ipm(P, &I, W);
         obstacle_t O;
         orc_obstacle_init(&O, gate12 + b * 12);
-        R[b * 9 + j] = reward_from_traj(P, &O, goal + b * 3, W->x, N, NULL);
+        R[b * 9 + j] = reward_from_traj(P, &O, goal + b * 3, W->x, N, NULL, NULL);
         if (status) status[b * 9 + j] = st;
         if (g_grad_iters) {
             g_grad_iters[b * 9 + j] = W->iters;

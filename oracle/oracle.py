@@ -85,6 +85,7 @@ def _bind(L):
         L.orc_pow15.argtypes = [ctypes.c_double]
         L.orc_solve_q.argtypes = [P(OrcParams), i64, pd, pd, pd, pd, pd, pd, pd, pd, pd, pd, pi, pi]
         L.orc_reward.argtypes = [P(OrcParams), i64, pd, pd, pd, pd, pi]
+        L.orc_reward_detail.argtypes = [P(OrcParams), i64, pd, pd, pd, pd, pi, pi]
         L.orc_collis_det.argtypes = [i64, ctypes.c_int, pd, pd, pd, pi, pi]
         L.orc_model_eval.argtypes = [P(OrcParams), i64, pd, pd, pd, pd, pd, pd, pd, pd]
         L.orc_cost_eval.argtypes = [P(OrcParams), i64, pd, pd, pd, pd, pd, pd, pd, pd, pd]
@@ -150,13 +151,46 @@ def solve(ini, goal, ptra, qtra, t, ulast=None, params=None, fast=False):
             "trials": cnt[:, 2]}
 
 
+def _reward_horizon(p):
+    """The reward's goal path term reads rows N-4..N-1 of the N+1 trajectory rows with numpy's wrap of negative
+    indices (quad_policy.py:88-89); at horizon 1 the reference itself raises IndexError (row -3 of 2)."""
+    if p.horizon < 2:
+        raise ValueError(f"the reward is undefined at horizon {p.horizon}: its path term reads row N-4 of N+1 rows "
+                         "(horizon >= 2 is required)")
+
+
+# crossing stage codes of reward_detail (orc_reward_detail) and its line-distance outcomes
+CROSS_NEVER, CROSS_BEHIND = -1, -2
+LD_NONE, LD_PERP, LD_END = 0, 1, 2
+
+
 def reward(x, goal, gate12, params=None):
     p = params or default_params()
+    _reward_horizon(p)
     x, goal, gate12 = _c(x), _c(goal).reshape(-1, 3), _c(gate12).reshape(-1, 12)
     B = goal.shape[0]
+    assert x.size == B * (p.horizon + 1) * NX, "x must be (B, horizon + 1, 13)"
     r = np.zeros(B); br = np.zeros((B, 4), np.int32)
-    lib().orc_reward(ctypes.byref(p), B, _ptr(x), _ptr(goal), _ptr(gate12), _ptr(r), _ptr(br, ctypes.c_int32))
+    rc = lib().orc_reward(ctypes.byref(p), B, _ptr(x), _ptr(goal), _ptr(gate12), _ptr(r), _ptr(br, ctypes.c_int32))
+    assert rc == 0
     return r, br
+
+
+def reward_detail(x, goal, gate12, params=None):
+    """reward() plus what the scorer decided per rotor: (reward (B,), branch (B, 4), cross (B, 4), ld (B, 4)).
+    cross: the first stage behind plane 1, CROSS_NEVER (-1) when no stage 0..N-1 is, CROSS_BEHIND (-2) when stage 0
+    is already.  ld: for frame (edge) branches, whether the minimum over the three line distances was the
+    perpendicular distance (LD_PERP) or an end-point distance (LD_END); LD_NONE for the other branches."""
+    p = params or default_params()
+    _reward_horizon(p)
+    x, goal, gate12 = _c(x), _c(goal).reshape(-1, 3), _c(gate12).reshape(-1, 12)
+    B = goal.shape[0]
+    assert x.size == B * (p.horizon + 1) * NX, "x must be (B, horizon + 1, 13)"
+    r = np.zeros(B); br = np.zeros((B, 4), np.int32); det = np.zeros((B, 4, 2), np.int32)
+    rc = lib().orc_reward_detail(ctypes.byref(p), B, _ptr(x), _ptr(goal), _ptr(gate12), _ptr(r),
+                                 _ptr(br, ctypes.c_int32), _ptr(det, ctypes.c_int32))
+    assert rc == 0
+    return r, br, det[:, :, 0].copy(), det[:, :, 1].copy()
 
 
 def collis_det(gate12, tracks):
@@ -194,6 +228,7 @@ def sol_gradient(ini, goal, gate12, dnn_out, ulast=None, params=None, fast=False
     fast=True runs the -O3 / FMA timing build (bench.py cpu_baseline).  iters: optional int32 (B, 9) array
     that receives every job's IPM iteration count (rewards9 slot order)."""
     p = params or default_params()
+    _reward_horizon(p)
     ini, goal, gate12 = _c(ini).reshape(-1, NX), _c(goal).reshape(-1, 3), _c(gate12).reshape(-1, 12)
     dnn = _c(dnn_out, np.float32).reshape(-1, 7)
     B = ini.shape[0]

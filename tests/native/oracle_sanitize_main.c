@@ -2,7 +2,8 @@
  * Built by tests/native/Makefile (target oracle_sanitize) as one translation unit with
  * oracle/lafse3_oracle.c, run by tests/test_sanitizers.py.  Exercises every exported entry point on a
  * small seeded batch (written by the test as raw float64: B, then ini B x 13, goal B x 3, gate12 B x 12,
- * dnn_out B x 7): both gradient modes, a shorter horizon, u_last, the reward/collision scorer, the
+ * dnn_out B x 7): both gradient modes, a shorter horizon, u_last, the reward/collision scorer (also at
+ * horizons 2 and 3 on exactly sized trajectories, and refused at horizon 1), the
  * model and cost derivatives, the trace/dump debug hooks.  Any sanitizer report aborts with a
  * non-zero exit (-fno-sanitize-recover=all); the values are checked by the other tests. */
 #include "../../oracle/lafse3_oracle.c"
@@ -109,6 +110,30 @@ int main(int argc, char **argv)
     orc_params P20 = P;
     P20.horizon = 20;
     bad |= orc_solve_q(&P20, B, ini, goal, pn, qn, tn, NULL, x, u, lam, cost, st, cnt);
+
+    /* the scorer at horizons 2 and 3, whose path term wraps rows N-4..N-1: trajectories, rewards and branch codes in
+     * heap blocks of exactly their size, so a row outside 0..N is a sanitizer report; horizon 1 is refused untouched */
+    static const int short_horizons[3] = {2, 3, 1};
+    for (int h = 0; h < 3; ++h) {
+        const int Ns = short_horizons[h];
+        orc_params Ps = P;
+        Ps.horizon = Ns;
+        const size_t nxs = (size_t)B * (Ns + 1) * NX;
+        double *xs_ = malloc(sizeof(double) * nxs), *Rs = malloc(sizeof(double) * B);
+        int32_t *brs = malloc(sizeof(int32_t) * B * 4), *det = malloc(sizeof(int32_t) * B * 8);
+        for (size_t i = 0; i < nxs; ++i) xs_[i] = x[i];   /* the first rows of the horizon-20 solutions */
+        for (int64_t b = 0; b < B; ++b) Rs[b] = -7.0;
+        const int rc1 = orc_reward(&Ps, B, xs_, goal, g12, Rs, brs);
+        const int rc2 = orc_reward_detail(&Ps, B, xs_, goal, g12, Rs, brs, det);
+        if (Ns == 1) {
+            bad |= (rc1 == 0) || (rc2 == 0) || (orc_sol_gradient(&Ps, B, ini, goal, g12, dnn, NULL, out8, NULL, NULL) == 0);
+            for (int64_t b = 0; b < B; ++b) bad |= Rs[b] != -7.0;
+        } else {
+            bad |= rc1 | rc2;
+            bad |= !all_finite(Rs, B);
+        }
+        free(xs_); free(Rs); free(brs); free(det);
+    }
 
     free(in); free(dnn); free(out8); free(R); free(st); free(ul); free(p); free(q); free(t); free(uu);
     free(x); free(u); free(lam); free(cost); free(cnt); free(pn); free(qn); free(tn); free(trace); free(dump);
