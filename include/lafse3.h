@@ -10,6 +10,7 @@
  *   lafse3_sol_gradient   replaces run_quad.sol_gradient      quad_policy.py:94-112
  *   lafse3_get_input      replaces run_quad.get_input         quad_policy.py:202-211
  *   lafse3_ocp_sensitivity  ocSolver + dx, du / d(p_tra, a_tra, t)  (the PDP auxiliary system, quad_OC.py:214-306)
+ *   lafse3_ocp_sensitivity_ex  the same with ini_state and goal columns and the feedback gain du_0 / dx_0
  *
  * Every array argument is a DEVICE pointer (HBM; e.g. a torch.cuda tensor's data_ptr()), owned by
  * the caller, row-major, contiguous.  B is the batch size.  N is params.horizon (<= LAFSE3_MAX_N).
@@ -140,6 +141,39 @@ int lafse3_ocp_sensitivity(lafse3_ctx *ctx, int64_t B, const double *ini_state, 
                            const double *p_tra, const double *a_tra, const double *t, const double *u_last,
                            double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
                            double *dx, double *du, int32_t *sens_status, void *stream);
+
+/* lafse3_ocp_sensitivity with selectable parameter groups and the MPC feedback gain.  The columns, in this fixed
+ * order and restricted to the groups selected in `groups`:
+ *   LAFSE3_SENS_THETA  p_tra[0..2], a_tra[0..2], t   7 columns, lafse3_ocp_sensitivity's bit for bit
+ *   LAFSE3_SENS_INI    ini_state[0..12]              13 columns; the quaternion entries are differentiated as the
+ *                                                    four raw numbers the solver reads (it does not normalise them)
+ *   LAFSE3_SENS_GOAL   goal[0..2]                    3 columns
+ * lafse3_sens_columns gives their number P = 7 [THETA] + 13 [INI] + 3 [GOAL] (LAFSE3_EINVAL for bits outside the
+ * three groups).  The first 14 arguments and the outputs x .. iters are lafse3_ocp_solve's, bit for bit.  Then, each
+ * nullable:
+ *   dx B x P x (N+1) x 13, du B x P x N x 4 as lafse3_ocp_sensitivity's; dx at stage 0 is the identity in the
+ *   ini_state columns and zero in the others;
+ *   gain B x 4 x P = du*_0[a] / dparam_q, the first control's row of du: over the ini_state columns it is the MPC
+ *   feedback gain du*_0 / dx_0 (4 x 13), the local linear policy around the current state;
+ *   sens_status B as lafse3_ocp_sensitivity's -- after 1 and 2 that instance's dx, du and gain are zero.
+ * With dx == du == gain == NULL the call is lafse3_ocp_solve; otherwise groups == 0 or a bit outside the three
+ * groups is LAFSE3_EINVAL.
+ * dx and du cost one refinement sweep per selected column, as lafse3_ocp_sensitivity.  gain is computed by the
+ * adjoint use of the same factorisation: the Newton matrix K is symmetric, so the sweep on the unit right-hand side
+ * of row (u_0, a) returns a column of -K^{-1}, and its dot product with dF/dparam_q is du*_0[a] / dparam_q: four
+ * sweeps for any P, and with dx == du == NULL nothing else.  u_last stays a constant: its influence on the optimum
+ * is too weak for a finite-difference check, and a column that cannot be checked is not offered.  A solver launch
+ * for lafse3_reserve, lafse3_last_kernel_ms, the counters and lafse3_check_device; it runs on the caller's stream
+ * and leaves the caller's current device alone. */
+#define LAFSE3_SENS_THETA 1   /* p_tra[0..2], a_tra[0..2], t : 7 columns */
+#define LAFSE3_SENS_INI   2   /* ini_state[0..12]            : 13 columns */
+#define LAFSE3_SENS_GOAL  4   /* goal[0..2]                  : 3 columns */
+int lafse3_sens_columns(int32_t groups);
+int lafse3_ocp_sensitivity_ex(lafse3_ctx *ctx, int64_t B, const double *ini_state, const double *goal,
+                              const double *p_tra, const double *a_tra, const double *t, const double *u_last,
+                              double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
+                              int32_t groups, double *dx, double *du, double *gain, int32_t *sens_status,
+                              void *stream);
 
 /* fp32 twin of lafse3_ocp_solve: the same arguments as float32 device buffers.  Inputs are
  * widened to fp64 and outputs rounded to fp32 on the device; the NLP itself is solved in fp64 (IPOPT's

@@ -17,6 +17,11 @@ VARIANT_WAVE = 1   # include/lafse3.h LAFSE3_VARIANT_WAVE (the only kernel varia
 STATUS_NAMES = {0: "solved", 1: "acceptable", 2: "max_iter", 3: "line_search_failed", 4: "non_finite",
                 5: "tiny_step", 6: "regularization_failed", 7: "device_error",
                 8: "restoration_failed", 9: "infeasible"}
+# include/lafse3.h LAFSE3_SENS_*: the parameter groups of lafse3_ocp_sensitivity_ex, in column order, and their columns
+SENS_GROUPS = {"theta": 1, "ini": 2, "goal": 4}
+SENS_COLUMNS = {"theta": ("p_tra[0]", "p_tra[1]", "p_tra[2]", "a_tra[0]", "a_tra[1]", "a_tra[2]", "t"),
+                "ini": tuple(f"ini_state[{i}]" for i in range(13)),
+                "goal": ("goal[0]", "goal[1]", "goal[2]")}
 
 
 class Params(ctypes.Structure):
@@ -59,6 +64,8 @@ SIGNATURES = {
     "lafse3_ocp_solve": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] * 6 + [_vp]),
     "lafse3_ocp_solve_f32": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] * 6 + [_vp]),
     "lafse3_ocp_sensitivity": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] * 6 + [_vp] * 3 + [_vp]),
+    "lafse3_sens_columns": (ctypes.c_int, [_i32]),
+    "lafse3_ocp_sensitivity_ex": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] * 6 + [_i32] + [_vp] * 4 + [_vp]),
     "lafse3_objective": (ctypes.c_int, [_vp, _i64] + [_vp] * 7 + [_vp, _vp, _vp]),
     "lafse3_sol_gradient": (ctypes.c_int, [_vp, _i64] + [_vp] * 5 + [_vp, _vp, _vp, _vp]),
     "lafse3_get_input": (ctypes.c_int, [_vp, _i64] + [_vp] * 4 + [_vp, _vp, _vp, _vp]),

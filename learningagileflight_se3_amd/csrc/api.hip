@@ -330,7 +330,7 @@ __global__ void slots_init_kernel(double *R, int32_t *S, int64_t n)
 }
 
 static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t sched_samples = 0,
-                  const lafse3::SensArgs *sens = nullptr)
+                  const lafse3::SensArgs *sens = nullptr, const lafse3::SensExArgs *sensx = nullptr)
 {
     if (A.n_inst == 0) return LAFSE3_OK;
     // trajectory scoring (MODE_REWARD) counts nothing and has its own queue head: it leaves the last solver
@@ -387,6 +387,7 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
     // the sensitivity pass is compiled into a kernel of its own (ipm_kernel.hip ipm_kernel_sens)
     // and so are the extra stores of a debug dump that carries the iterate (ipm_kernel_dump: plain solves only)
     if (sens) hipLaunchKernelGGL(lafse3::ipm_kernel_sens, dim3((unsigned)grid), dim3(64), 0, st, A, *sens);
+    else if (sensx) hipLaunchKernelGGL(lafse3::ipm_kernel_sens_ex, dim3((unsigned)grid), dim3(64), 0, st, A, *sensx);
     else if (A.dump && A.mode == lafse3::MODE_SOLVE && !A.sched)
         hipLaunchKernelGGL(lafse3::ipm_kernel_dump, dim3((unsigned)grid), dim3(64), 0, st, A);
     else hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
@@ -404,10 +405,12 @@ static lafse3::KernelArgs blank_args()
     return A;
 }
 
-// lafse3_ocp_solve and, with sens, lafse3_ocp_sensitivity: the one place that fills the MODE_SOLVE arguments
+// lafse3_ocp_solve and, with sens or sensx, lafse3_ocp_sensitivity / _ex: the one place that fills the MODE_SOLVE
+// arguments
 static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
                  const double *a_tra, const double *t, const double *u_last, double *x, double *u, double *lam,
-                 double *cost, int32_t *status, int32_t *iters, void *stream, const lafse3::SensArgs *sens)
+                 double *cost, int32_t *status, int32_t *iters, void *stream, const lafse3::SensArgs *sens,
+                 const lafse3::SensExArgs *sensx = nullptr)
 {
     if (const int rc = check_call(c, B, {ini, goal, p_tra, a_tra, t})) return rc;
     if (B == 0) return LAFSE3_OK;
@@ -418,7 +421,7 @@ static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal
     A.n_inst = B;
     A.ini = ini; A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;
     A.x_out = x; A.u_out = u; A.lam_out = lam; A.cost_out = cost; A.status_out = status; A.iters_out = iters;
-    return launch(c, A, (hipStream_t)stream, 0, sens);
+    return launch(c, A, (hipStream_t)stream, 0, sens, sensx);
 }
 
 int lafse3_ocp_solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
@@ -438,6 +441,33 @@ int lafse3_ocp_sensitivity(lafse3_ctx *c, int64_t B, const double *ini, const do
     // without dx and du the call is lafse3_ocp_solve
     return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream,
                  dx || du ? &Z : nullptr);
+}
+
+static_assert(LAFSE3_SENS_THETA == lafse3::SENS_G_THETA && LAFSE3_SENS_INI == lafse3::SENS_G_INI &&
+              LAFSE3_SENS_GOAL == lafse3::SENS_G_GOAL, "sens_ex.inc reads the header's group bits");
+
+int lafse3_sens_columns(int32_t groups)
+{
+    if (groups & ~(LAFSE3_SENS_THETA | LAFSE3_SENS_INI | LAFSE3_SENS_GOAL))
+        return fail(LAFSE3_EINVAL, "lafse3_sens_columns: bits outside LAFSE3_SENS_THETA | _INI | _GOAL");
+    return lafse3::sens_ex_columns(groups);
+}
+
+int lafse3_ocp_sensitivity_ex(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
+                              const double *a_tra, const double *t, const double *u_last, double *x, double *u,
+                              double *lam, double *cost, int32_t *status, int32_t *iters, int32_t groups, double *dx,
+                              double *du, double *gain, int32_t *sens_status, void *stream)
+{
+    if (!c) return fail(LAFSE3_EINVAL, "bad ctx / batch");
+    // without dx, du and gain the call is lafse3_ocp_solve
+    if (!dx && !du && !gain)
+        return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr);
+    if (groups == 0 || (groups & ~(LAFSE3_SENS_THETA | LAFSE3_SENS_INI | LAFSE3_SENS_GOAL)))
+        return fail(LAFSE3_EINVAL, "lafse3_ocp_sensitivity_ex: groups must be a non-empty subset of "
+                                   "LAFSE3_SENS_THETA | LAFSE3_SENS_INI | LAFSE3_SENS_GOAL");
+    lafse3::SensExArgs Z;
+    Z.dx_out = dx; Z.du_out = du; Z.gain_out = gain; Z.sens_out = sens_status; Z.groups = groups;
+    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr, &Z);
 }
 
 // ---- fp32 twin of lafse3_ocp_solve: float inputs/outputs at the boundary, fp64 arithmetic inside (IPOPT's

@@ -167,6 +167,13 @@ struct SensArgs {
     double *dx_out, *du_out;        // B x 7 x (N+1) x 13, B x 7 x N x 4 (each nullable)
     int32_t *sens_out;              // B: 0 ok, 1 the solve did not converge, 2 wrong inertia at z* (nullable)
 };
+// second argument of ipm_kernel_sens_ex (sens_ex.inc): P = the columns of the selected groups
+struct SensExArgs {
+    double *dx_out, *du_out;        // B x P x (N+1) x 13, B x P x N x 4 (each nullable)
+    double *gain_out;               // B x 4 x P (nullable)
+    int32_t *sens_out;              // as SensArgs::sens_out
+    int32_t groups;                 // LAFSE3_SENS_THETA | _INI | _GOAL
+};
 
 struct Ctl {
     int N;
@@ -1823,6 +1830,7 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 }
 
 #include "sens.inc"
+#include "sens_ex.inc"
 
 // ------------------------------------------------------------------------------------------------
 // waves per SIMD the register allocation targets (LDS admits 2: Smem <= 20 KB)
@@ -1830,9 +1838,11 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 // Returns the instance's IPM iteration count (0 for trajectory scoring).
 // SENS (ipm_kernel_sens): the sensitivity pass of sens.inc follows a MODE_SOLVE instance; ipm_kernel compiles none of it.
 // DUMP (ipm_kernel_dump): the debug dump also records the iterate (dump_point); ipm_kernel compiles none of that.
-template <bool SENS, bool DUMP = false>
+// SENSX (ipm_kernel_sens_ex): the pass of sens_ex.inc follows a MODE_SOLVE instance, as SENS.
+template <bool SENS, bool DUMP = false, bool SENSX = false>
 __device__ __attribute__((always_inline)) inline int run_instance(const KernelArgs &A, Smem &S, const int64_t inst,
-                                                                 gdouble *ws, const SensArgs *Z = nullptr)
+                                                                 gdouble *ws, const SensArgs *Z = nullptr,
+                                                                 const SensExArgs *ZX = nullptr)
 {
     const int lane = lane_id();
     const lafse3_params &prm = A.prm;
@@ -2483,6 +2493,16 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
             if (lane == 0 && Z->sens_out) Z->sens_out[inst] = sst;
         }
     }
+    if constexpr (SENSX) {
+        if (A.mode == MODE_SOLVE && (ZX->dx_out || ZX->du_out || ZX->gain_out)) {
+            const int64_t P = sens_ex_columns(ZX->groups);
+            const int sst = sens_ex_pass(prm, M, S, C, ws, a3, tt, status <= 1, ZX->groups,
+                                         ZX->dx_out ? ZX->dx_out + inst * P * (N + 1) * NX : nullptr,
+                                         ZX->du_out ? ZX->du_out + inst * P * N * NU : nullptr,
+                                         ZX->gain_out ? ZX->gain_out + inst * NU * P : nullptr);
+            if (lane == 0 && ZX->sens_out) ZX->sens_out[inst] = sst;
+        }
+    }
     PT_END(S, 10);
 #ifdef LAFSE3_PHASE_TIMERS
     if (A.ptime && lane < 16) A.ptime[inst * PT_COLS + lane] = S.pt[lane];
@@ -2689,6 +2709,24 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_dump(KernelArgs A)
         KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         __asm__ volatile("" : "+s"(Ap));
         run_instance<false, true>(*(const KernelArgs *)Ap, S, inst, ws);
+    }
+}
+
+// The persistent solver with the pass of sens_ex.inc compiled in (lafse3_ocp_sensitivity_ex only): as ipm_kernel_sens
+// a further instantiation of run_instance in a kernel of its own with the plain queue-head loop.
+__global__ __launch_bounds__(64, 1) void ipm_kernel_sens_ex(KernelArgs A, SensExArgs Z)
+{
+    Smem &S = instance_smem();
+    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
+    for (;;) {
+        unsigned long long v = 0ull;
+        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
+        const int64_t inst = bcast_i64((int64_t)v);
+        if (inst >= A.n_inst) break;
+        typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
+        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+        __asm__ volatile("" : "+s"(Ap));
+        run_instance<false, false, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, &Z);
     }
 }
 

@@ -1,0 +1,213 @@
+// sens_ex.inc — sensitivities of a finished MODE_SOLVE instance to theta, ini_state and goal, and the MPC feedback
+// gain (lafse3_ocp_sensitivity_ex; #included by ipm_kernel.hip after sens.inc, compiled into ipm_kernel_sens_ex only).
+//
+// Columns, in this order, restricted to the selected groups (LAFSE3_SENS_THETA | _INI | _GOAL):
+//   theta       p_tra[0..2], a_tra[0..2], t   7   x rows k = 1..N-1, exactly sens.inc's
+//   ini_state   ini_state[0..12]             13   stage 0 only (x_0 is not a decision variable): dynamics rows
+//                                                 A_0 e_i, u rows the q-u cross term of the Lagrangian Hessian
+//                                                 (StageHess::qu from lam_0, the same value for every rotor)
+//   goal        goal[0..2]                    3   x rows k = 1..N, position row i: -2 wrf s (state_cost_grad's
+//                                                 goal term; the terminal cost carries the same weight, and the
+//                                                 attitude-to-goal term has a fixed target)
+// Each is dF/dparam_q of the KKT system F(z, param) = 0 in the three row blocks linear_solve reads (x rows WS_RQ,
+// u rows WS_RR, dynamics rows WS_RC); a chain sweep on the right-hand side r returns d = -K^{-1} r in
+// (dx, du, lam+), so dz*/dparam_q is the sweep's result as it stands (sens.inc).
+//
+// Forward route (dx, du): one sweep per selected column.
+// Adjoint route (gain = du*_0 / dparam, 4 x P): K is symmetric (row blocks x, u, dynamics against the unknowns dx,
+// du, lam+), so the sweep on r = e_(u_0, a) returns d_a = -K^{-1} e_(u_0, a), and
+//   du*_0[a] / dparam_q = e^T (-K^{-1} c_q) = d_a . c_q
+// summed over the three blocks: dx against the x rows, du against the u rows, lam+ (what costates_identity<false>
+// with fac = 0 leaves in lamp, the sweep's own sign) against the dynamics rows.  Four sweeps for any number of
+// columns.  The ini_state columns live on stage 0 alone, so their contraction is A_0^T lam+_0 (At_times) plus qu
+// times the sum of du_0.
+// u_last stays a constant: its influence on the optimum is too weak for a finite-difference yardstick.
+constexpr int SENS_EX_NP = 23;
+constexpr int SENS_G_THETA = 1, SENS_G_INI = 2, SENS_G_GOAL = 4;
+
+__host__ __device__ inline int sens_ex_columns(int groups)
+{
+    return ((groups & SENS_G_THETA) ? 7 : 0) + ((groups & SENS_G_INI) ? NX : 0) + ((groups & SENS_G_GOAL) ? 3 : 0);
+}
+
+// dF/dparam at stage k (the caller's lane, k <= N) of column i of group grp: vx the x rows (k >= 1), vu the u rows
+// and vc the dynamics rows (k < N); the sign and the objective scaling C.s are sens_pass's.
+__device__ __attribute__((always_inline)) inline void sens_column(const lafse3_params &prm, const Model &M,
+                                                                  const Smem &S, const Ctl &C, const double *a3,
+                                                                  double tt, int grp, int q, int k, double *vx,
+                                                                  double *vu, double *vc)
+{
+    const int N = C.N;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) vx[i] = vc[i] = 0.0;
+#pragma unroll
+    for (int a = 0; a < NU; ++a) vu[a] = 0.0;
+    if (grp == SENS_G_THETA) {
+        if (k >= 1 && k < N) {
+            if (q < 6) {
+                tra_grad_fd(M, S, C, a3, q, k, vx);
+            } else {
+                double xk[NX], g1[NX], g0[NX];
+                load_stage(S, k, xk);
+                state_cost_grad(M, S.at, S.goal, S.ptra, 1.0, xk, g1);
+                state_cost_grad(M, S.at, S.goal, S.ptra, 0.0, xk, g0);
+                const double dwk = 2 * prm.tra_w_decay * (prm.dt * k - tt) * S.wk[k];
+#pragma unroll
+                for (int i = 0; i < NX; ++i) vx[i] = C.s * dwk * (g1[i] - g0[i]);
+            }
+        }
+    } else if (grp == SENS_G_GOAL) {
+        if (k >= 1) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) vx[i] = (i == q) ? -2 * M.wrf * C.s : 0.0;
+        }
+    } else if (k == 0) {
+        double x0[NX], u0[NU], l0[NX], e[NX];
+        load_stage(S, 0, x0);
+        load_u(S, 0, u0);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            l0[i] = S.lam[i * SX];
+            e[i] = (i == q) ? 1.0 : 0.0;
+        }
+        A_times(M, x0, u0, e, vc);
+        StageHess H;
+        stage_hessian(M, S.at, C.s, 0.0, x0, u0, l0, H);
+        const double hq = (q >= 6 && q < 10) ? sel4(q - 6, H.qu[0], H.qu[1], H.qu[2], H.qu[3]) : 0.0;
+#pragma unroll
+        for (int a = 0; a < NU; ++a) vu[a] = hq;
+    }
+}
+
+// The outputs of one instance: dxo P x (N+1) x 13, duo P x N x 4, gno 4 x P (each nullable), P the selected
+// columns.  `ok`: the solve ended solved or acceptable.  Returns the instance's sens_status (sens.inc); the
+// outputs are zero unless it is SENS_OK.
+__device__ __noinline__ int sens_ex_pass(const lafse3_params &prm, const Model &M, Smem &S, const Ctl &C, gdouble *ws,
+                                         const double *a3, double tt, int ok, int groups, double *dxo, double *duo,
+                                         double *gno)
+{
+    WS_TRAJ(ws);
+    const int lane = lane_id();
+    const int N = C.N;
+    const int P = sens_ex_columns(groups);
+    gdouble *rq = ws + WS_RQ, *rr = ws + WS_RR, *rc = ws + WS_RC;
+    int st = ok ? SENS_OK : SENS_UNCONVERGED;
+    if (ok) {
+        int sw = 0;
+        double rat[4];
+        if (!linear_solve(M, S.at, S, C, ws, 0.0, 1, 0, 0, 0, sw, rat, nullptr)) st = SENS_INERTIA;
+    }
+    for (int e = lane; e < NU * SX; e += WAVE) rr[e] = 0.0;
+    for (int e = lane; e < NX * SX; e += WAVE) rc[e] = 0.0;
+    vm_sync();
+    // ---- forward route: one sweep per selected column
+    if (dxo || duo) {
+        int col = 0;
+        for (int grp = SENS_G_THETA; grp <= SENS_G_GOAL; grp <<= 1) {
+            if (!(groups & grp)) continue;
+            const int nq = (grp == SENS_G_THETA) ? 7 : (grp == SENS_G_INI ? NX : 3);
+            for (int q = 0; q < nq; ++q, ++col) {
+                if (st == SENS_OK) {
+                    if (lane <= N) {
+                        const int k = lane;
+                        double vx[NX], vu[NU], vc[NX];
+                        sens_column(prm, M, S, C, a3, tt, grp, q, k, vx, vu, vc);
+#pragma unroll
+                        for (int i = 0; i < NX; ++i) rq[i * SX + k] = vx[i];
+                        if (k < N) {   // zero again behind an ini_state column
+#pragma unroll
+                            for (int a = 0; a < NU; ++a) rr[a * SX + k] = vu[a];
+#pragma unroll
+                            for (int i = 0; i < NX; ++i) rc[i * SX + k] = vc[i];
+                        }
+                    }
+                    vm_sync();
+                    int sw = 0;
+                    double rat[4];
+                    linear_solve(M, S.at, S, C, ws, 0.0, 0, 0, 0, 0, sw, rat, nullptr);
+                    sync();
+                }
+                // LDS SoA [i][k] -> stage-major [k][i]; every index is below (N+1) * 13 resp. N * 4 of this column's
+                // block.  Stage 0 of dx is the identity in the ini_state columns and zero otherwise.
+                if (dxo) {
+                    double *o = dxo + (int64_t)col * (N + 1) * NX;
+                    for (int e = lane; e < (N + 1) * NX; e += WAVE) {
+                        double v = 0.0;
+                        if (st == SENS_OK) v = (e >= NX) ? DX[(e % NX) * SX + e / NX]
+                                                         : ((grp == SENS_G_INI && e == q) ? 1.0 : 0.0);
+                        o[e] = v;
+                    }
+                }
+                if (duo) {
+                    double *o = duo + (int64_t)col * N * NU;
+                    for (int e = lane; e < N * NU; e += WAVE) o[e] = (st == SENS_OK) ? DU[(e % NU) * SX + e / NU] : 0.0;
+                }
+            }
+        }
+    }
+    // ---- adjoint route: one sweep per control of stage 0
+    if (gno) {
+        if (st != SENS_OK) {
+            for (int e = lane; e < NU * P; e += WAVE) gno[e] = 0.0;
+            return st;
+        }
+        for (int a = 0; a < NU; ++a) {
+            for (int e = lane; e < NX * SX; e += WAVE) {
+                rq[e] = 0.0;
+                rc[e] = 0.0;
+            }
+            for (int e = lane; e < NU * SX; e += WAVE) rr[e] = (e == a * SX) ? 1.0 : 0.0;
+            vm_sync();
+            int sw = 0;
+            double rat[4];
+            linear_solve(M, S.at, S, C, ws, 0.0, 0, 0, 0, 0, sw, rat, nullptr);
+            sync();
+            double *o = gno + (int64_t)a * P;
+            int col = 0;
+            for (int grp = SENS_G_THETA; grp <= SENS_G_GOAL; grp <<= 1) {
+                if (!(groups & grp)) continue;
+                if (grp == SENS_G_INI) {
+                    // stage 0 only: (A_0^T lam+_0)_i + qu_i (du_0[0] + .. + du_0[3]), the same in every lane
+                    double x0[NX], u0[NU], l0[NX], lp0[NX], atl[NX];
+                    load_stage(S, 0, x0);
+                    load_u(S, 0, u0);
+#pragma unroll
+                    for (int i = 0; i < NX; ++i) {
+                        l0[i] = LAM[i * SX];
+                        lp0[i] = LP[i * SX];
+                    }
+                    At_times(M, x0, u0, lp0, atl);
+                    StageHess H;
+                    stage_hessian(M, S.at, C.s, 0.0, x0, u0, l0, H);
+                    double sdu = 0.0;
+#pragma unroll
+                    for (int b = 0; b < NU; ++b) sdu += DU[b * SX];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) atl[6 + i] += H.qu[i] * sdu;
+                    if (lane < NX) {
+                        double v = atl[0];
+#pragma unroll
+                        for (int i = 1; i < NX; ++i) v = (lane == i) ? atl[i] : v;
+                        o[col + lane] = v;
+                    }
+                    col += NX;
+                    continue;
+                }
+                const int nq = (grp == SENS_G_THETA) ? 7 : 3;
+                for (int q = 0; q < nq; ++q, ++col) {
+                    double acc = 0.0;
+                    if (lane >= 1 && lane <= N) {   // theta and goal columns have x rows only
+                        const int k = lane;
+                        double vx[NX], vu[NU], vc[NX];
+                        sens_column(prm, M, S, C, a3, tt, grp, q, k, vx, vu, vc);
+#pragma unroll
+                        for (int i = 0; i < NX; ++i) acc = fma(DX[i * SX + k], vx[i], acc);
+                    }
+                    acc = wsum(acc);
+                    if (lane == 0) o[col] = acc;
+                }
+            }
+        }
+    }
+    return st;
+}

@@ -10,6 +10,11 @@ the incoming gradients.  This is the derivative the reference sketched as the PD
 The derivative is that of the barrier problem at the solver's final mu: across an active-set change it is a
 one-sided smoothing, not a subgradient.  Instances whose sensitivity is not available (the solve did not converge,
 or the factorisation at the optimum met a wrong inertia: ``sens_status != 0``) contribute a zero gradient.
+
+When ``ini_state`` or ``goal`` requires a gradient, ``mpc_layer`` goes through ``Engine.ocp_sensitivity_ex`` instead,
+which also has their columns, and ``mpc_policy`` returns the first control u*_0 with a gradient to all five inputs from
+the feedback gain alone (include/lafse3.h lafse3_ocp_sensitivity_ex): the layer for closed-loop rollouts.  u_last is
+a constant throughout.
 """
 from __future__ import annotations
 
@@ -68,6 +73,110 @@ class MPCFunction(torch.autograd.Function):
         return (None, None, None, out[0], out[1], out[2], None)
 
 
+# The parameter groups of Engine.ocp_sensitivity_ex in column order, each with its columns and the positions of
+# its inputs among (ini_state, goal, p_tra, a_tra, t) and their column ranges inside the group.
+_GROUPS = (("theta", 7, ((2, 0, 3), (3, 3, 6), (4, 6, 7))), ("ini", 13, ((0, 0, 13),)), ("goal", 3, ((1, 0, 3),)))
+
+
+def _needed_groups(needs):
+    """needs: needs_input_grad of (ini_state, goal, p_tra, a_tra, t) -> the groups with an input that needs one."""
+    return tuple(name for name, _, members in _GROUPS if any(needs[i] for i, _, _ in members))
+
+
+def _meta(v):
+    return (v.dtype, v.shape, v.device) if isinstance(v, torch.Tensor) else None
+
+
+def _scatter_columns(g, groups, metas, needs):
+    """g (B, P): the gradient w.r.t. the P columns of ``groups`` -> the gradients of (ini_state, goal, p_tra, a_tra,
+    t) in their dtype, shape and device; None for an input that is no tensor or needs none."""
+    out = [None] * 5
+    col = 0
+    for name, n, members in _GROUPS:
+        if name not in groups:
+            continue
+        for i, lo, hi in members:
+            if metas[i] is None or not needs[i]:
+                continue
+            dtype, shape, device = metas[i]
+            gi = g[:, col + lo:col + hi]
+            # an input of one row (a scalar t) was broadcast over the batch: sum its gradient back
+            gi = gi if gi.numel() == shape.numel() else gi.sum(0)
+            out[i] = gi.reshape(shape).to(device=device, dtype=dtype)
+        col += n
+    return out
+
+
+class MPCFunctionEx(torch.autograd.Function):
+    """MPCFunction with gradients to ini_state and goal as well: (engine, ini_state, goal, p_tra, a_tra, t, u_last)
+    -> (x, u, status).  One ``Engine.ocp_sensitivity_ex`` launch that asks for only the parameter groups with an
+    input that needs a gradient; each such input receives its gradient in its own dtype and shape.  u_last and the
+    engine get none.  The quaternion entries of ini_state are differentiated as the four raw numbers the solver
+    reads."""
+
+    @staticmethod
+    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last=None):
+        needs = ctx.needs_input_grad[1:6]
+        ctx.groups = _needed_groups(needs)
+        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t))
+        want = ("x", "u", "dx", "du") if ctx.groups else ("x", "u")
+        out = engine.ocp_sensitivity_ex(ini_state, goal, p_tra, a_tra, t, u_last, groups=ctx.groups or ("theta",),
+                                        want=want)
+        if ctx.groups:
+            ctx.save_for_backward(out["dx"], out["du"], out["sens_status"])
+        ctx.mark_non_differentiable(out["status"])
+        return out["x"], out["u"], out["status"]
+
+    @staticmethod
+    def backward(ctx, g_x, g_u, _g_status):
+        dx, du, sens_status = ctx.saved_tensors
+        g = torch.zeros(dx.shape[:2], dtype=dx.dtype, device=dx.device)
+        if g_x is not None:
+            g = g + torch.einsum("bqki,bki->bq", dx, g_x.to(dx.dtype))
+        if g_u is not None:
+            g = g + torch.einsum("bqka,bka->bq", du, g_u.to(du.dtype))
+        g = torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
+        return (None, *_scatter_columns(g, ctx.groups, ctx.metas, ctx.needs_input_grad[1:6]), None)
+
+
+class MPCPolicyFunction(torch.autograd.Function):
+    """(engine, ini_state, goal, p_tra, a_tra, t, u_last) -> (u0 (B, 4), status (B,)): the first control of the
+    optimum, differentiable in ini_state, goal, p_tra, a_tra and t through ``gain`` alone (four adjoint sweeps on the
+    factorisation at the optimum; no dx, no du).  Over ini_state the Jacobian is the MPC feedback gain."""
+
+    @staticmethod
+    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last=None):
+        needs = ctx.needs_input_grad[1:6]
+        ctx.groups = _needed_groups(needs)
+        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t))
+        out = engine.ocp_sensitivity_ex(ini_state, goal, p_tra, a_tra, t, u_last, groups=ctx.groups or ("theta",),
+                                        want=("u", "gain") if ctx.groups else ("u",))
+        if ctx.groups:
+            ctx.save_for_backward(out["gain"], out["sens_status"])
+        ctx.mark_non_differentiable(out["status"])
+        return out["u"][:, 0].contiguous(), out["status"]
+
+    @staticmethod
+    def backward(ctx, g_u0, _g_status):
+        gain, sens_status = ctx.saved_tensors
+        g = torch.einsum("baq,ba->bq", gain, g_u0.to(gain.dtype))
+        g = torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
+        return (None, *_scatter_columns(g, ctx.groups, ctx.metas, ctx.needs_input_grad[1:6]), None)
+
+
+def _wants_grad(v):
+    return isinstance(v, torch.Tensor) and v.requires_grad
+
+
 def mpc_layer(engine, ini_state, goal, p_tra, a_tra, t, u_last=None):
-    """Differentiable batched MPC solve -> (x, u, status); see MPCFunction."""
+    """Differentiable batched MPC solve -> (x, u, status); see MPCFunction.  When ini_state or goal is a tensor that
+    requires a gradient, the solve goes through MPCFunctionEx, which also returns gradients to them."""
+    if _wants_grad(ini_state) or _wants_grad(goal):
+        return MPCFunctionEx.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last)
     return MPCFunction.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last)
+
+
+def mpc_policy(engine, ini_state, goal, p_tra, a_tra, t, u_last=None):
+    """The MPC policy u0 = u*_0(ini_state, goal, p_tra, a_tra, t) -> (u0 (B, 4), status), differentiable in all five
+    (see MPCPolicyFunction): the layer for closed-loop rollouts x_{t+1} = plant(x_t, u0(x_t, ..))."""
+    return MPCPolicyFunction.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last)

@@ -10,6 +10,7 @@ Reference interfaces mirrored (yanrui89/LearningAgileFlight_SE3):
   Engine.sol_gradient  run_quad.sol_gradient   quad_policy.py:94-112
   Engine.get_input     run_quad.get_input      quad_policy.py:202-211
   Engine.ocp_sensitivity  ocSolver + dx*/dtheta, du*/dtheta (the PDP auxiliary system sketched in quad_OC.py:214-306)
+  Engine.ocp_sensitivity_ex  the same with ini_state and goal columns and the MPC feedback gain du*_0/dx_0
 """
 from __future__ import annotations
 
@@ -278,6 +279,52 @@ class Engine:
                                              _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["dx"]), _ptr(out["du"]),
                                              _ptr(out.get("sens_status")), self._stream()), "lafse3_ocp_sensitivity")
         return {k: v for k, v in out.items() if v is not None}
+
+    def ocp_sensitivity_ex(self, ini_state, goal, p_tra, a_tra, t, u_last=None, groups=("theta", "ini", "goal"),
+                           want=("x", "u", "dx", "du", "gain")):
+        """ocp_sensitivity with selectable parameter groups and the MPC feedback gain (lafse3_ocp_sensitivity_ex),
+        one launch.
+
+        ``groups``: any of "theta" (p_tra, a_tra, t: 7 columns), "ini" (ini_state: 13), "goal" (3), or the
+        LAFSE3_SENS_* bit mask; the P columns come in that fixed order whatever the order given.  Returns
+        ocp_sensitivity's dict with dx (B, P, N+1, 13), du (B, P, N, 4) and
+          gain (B, 4, P) = du_0[a] / dparam_q, over the "ini" columns the feedback gain du*_0 / dx_0,
+          columns: the P column names in order ("p_tra[0]", .., "ini_state[0]", .., "goal[2]").
+        dx and du cost one sweep per column, gain four sweeps in all; want=("gain",) computes nothing else.
+        After sens_status != 0 an instance's dx, du and gain are zero.  float64 only."""
+        if isinstance(groups, str):
+            groups = (groups,)
+        if isinstance(groups, int):
+            mask = int(groups)
+        else:
+            unknown = [g for g in groups if g not in _lib.SENS_GROUPS]
+            if unknown:
+                raise ValueError(f"groups: unknown {unknown}; expected any of {list(_lib.SENS_GROUPS)}")
+            mask = sum(bit for g, bit in _lib.SENS_GROUPS.items() if g in groups)
+        sens = any(k in want for k in ("dx", "du", "gain"))
+        if sens and (mask == 0 or mask & ~sum(_lib.SENS_GROUPS.values())):
+            raise ValueError(f"groups: {groups!r} selects no column or a bit outside {_lib.SENS_GROUPS}")
+        columns = [c for g, bit in _lib.SENS_GROUPS.items() if mask & bit for c in _lib.SENS_COLUMNS[g]]
+        P = len(columns)
+        d, f64 = self.device, torch.float64
+        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
+        N = self.horizon
+        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,),
+                  "dx": (B, P, N + 1, NX), "du": (B, P, N, NU), "gain": (B, NU, P)}
+        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
+        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
+        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
+        if any(out[k] is not None for k in ("dx", "du", "gain")):   # without any the call is lafse3_ocp_solve
+            out["sens_status"] = torch.empty((B,), dtype=torch.int32, device=d)
+        check(self._L.lafse3_ocp_sensitivity_ex(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt),
+                                                _ptr(ul), _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]),
+                                                _ptr(out["cost"]), _ptr(out["status"]), _ptr(out["iters"]), mask,
+                                                _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["gain"]),
+                                                _ptr(out.get("sens_status")), self._stream()),
+              "lafse3_ocp_sensitivity_ex")
+        res = {k: v for k, v in out.items() if v is not None}
+        res["columns"] = columns
+        return res
 
     def objective(self, ini_state, goal, gate12, p_tra, a_tra, t, u_last=None):
         """Batched run_quad.objective -> (reward (B,), status (B,))."""
