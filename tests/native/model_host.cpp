@@ -18,11 +18,12 @@ extern "C" {
 // For n points: f (13), A (13x13) and B (13x4) assembled column-by-column from A_times / B_times,
 // A^T (13x13) from At_times, B^T from Bt_times, lambda-Hessian (13x13 via Hxx_times on unit vectors
 // with zero cost weights) and the q-u coupling vector.
-int model_host_eval(int n, const double *x, const double *u, const double *lam, double *f, double *A, double *B,
-                    double *At, double *Bt, double *Hl, double *qu)
+// model_host_eval_p takes the parameters (the model constants and weights of lafse3_params); model_host_eval is the
+// same at the reference's.
+int model_host_eval_p(const lafse3_params *prm, int n, const double *x, const double *u, const double *lam, double *f,
+                      double *A, double *B, double *At, double *Bt, double *Hl, double *qu)
 {
-    lafse3_params p = defaults();
-    Model M = make_model(p);
+    Model M = make_model(*prm);
     Attitude at{};
     at.trRt = at.trRg = 3.0;
     for (int i = 0; i < n; ++i) {
@@ -64,12 +65,18 @@ int model_host_eval(int n, const double *x, const double *u, const double *lam, 
     return 0;
 }
 
-// state cost gradient / Hessian (through stage_hessian + Hxx_times with lam = 0)
-int model_host_cost(int n, const double *x, const double *goal, const double *ptra, const double *qtra,
-                    const double *wk, double *path, double *tra, double *grad, double *hess)
+int model_host_eval(int n, const double *x, const double *u, const double *lam, double *f, double *A, double *B,
+                    double *At, double *Bt, double *Hl, double *qu)
 {
     lafse3_params p = defaults();
-    Model M = make_model(p);
+    return model_host_eval_p(&p, n, x, u, lam, f, A, B, At, Bt, Hl, qu);
+}
+
+// state cost gradient / Hessian (through stage_hessian + Hxx_times with lam = 0); the goal attitude is the identity
+int model_host_cost_p(const lafse3_params *prm, int n, const double *x, const double *goal, const double *ptra,
+                      const double *qtra, const double *wk, double *path, double *tra, double *grad, double *hess)
+{
+    Model M = make_model(*prm);
     for (int i = 0; i < n; ++i) {
         double Rt[9], Rg[9], St[16], Sg[16];
         dcm(qtra + i * 4, Rt);
@@ -100,5 +107,12 @@ int model_host_cost(int n, const double *x, const double *goal, const double *pt
         }
     }
     return 0;
+}
+
+int model_host_cost(int n, const double *x, const double *goal, const double *ptra, const double *qtra,
+                    const double *wk, double *path, double *tra, double *grad, double *hess)
+{
+    lafse3_params p = defaults();
+    return model_host_cost_p(&p, n, x, goal, ptra, qtra, wk, path, tra, grad, hess);
 }
 }

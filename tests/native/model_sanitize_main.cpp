@@ -41,6 +41,20 @@ int main()
     int bad = rc != 0;
     for (double v : A) bad |= !std::isfinite(v);
     for (double v : hess) bad |= !std::isfinite(v);
+    // the same points at parameters where Model::az and the goal-attitude branches (wqf) are live: the model constants
+    // and weights of GENERIC in tests/generic_params.py, which is their source (keep this copy equal to it); its
+    // tra_w_peak, tra_w_decay and the four bounds are not read by anything this program calls
+    lafse3_params g = defaults();
+    g.mass = 0.6; g.Jx = 0.0021; g.Jy = 0.0029; g.Jz = 0.0043; g.arm_l = 0.30; g.c_tau = 0.03; g.grav = 9.81;
+    g.dt = 0.08; g.wrt = 4; g.wqt = 60; g.wthrust = 0.15; g.wrf = 6; g.wvf = 4; g.wqf = 2; g.wwf = 2.5;
+    g.du_weight = 0.7;
+    rc = model_host_eval_p(&g, n, x.data(), u.data(), lam.data(), f.data(), A.data(), B.data(), At.data(), Bt.data(),
+                           Hl.data(), qu.data());
+    rc |= model_host_cost_p(&g, n, x.data(), goal.data(), ptra.data(), qtra.data(), wk.data(), path.data(), tra.data(),
+                            grad.data(), hess.data());
+    bad |= rc != 0;
+    for (double v : A) bad |= !std::isfinite(v);
+    for (double v : hess) bad |= !std::isfinite(v);
     std::printf("model_sanitize %s (n=%d)\n", bad ? "FAILED" : "ok", n);
     return bad;
 }

@@ -22,6 +22,9 @@ Sign convention of the multipliers: CasADi's lam_g, L = J + lam^T c with c as ab
 s_obj is IPOPT's gradient-based scaling, 100 / max|grad J| at the initial point when that maximum exceeds 100
 (floored at 1e-8), recomputed here by autograd at the initial point: U at the bound midpoint, X_k = 0 (k >= 1),
 both pushed 1e-2 inside the relaxed bounds.
+
+`initial_point` and `NewtonSystem` take an optional `prm` (kkt.Problem: model constants, weights, bounds, possibly
+asymmetric); the default is the reference's problem.
 """
 from __future__ import annotations
 
@@ -47,6 +50,11 @@ U_LO, U_HI = _relax(0.0, kkt.U_UB)
 W_LO, W_HI = _relax(-kkt.W_UB, kkt.W_UB)
 
 
+def relaxed_bounds(prm=kkt.DEFAULT):
+    """(u_lo, u_hi, w_lo, w_hi): the boxes of prm, each side relaxed by 1e-8 max(1, |bound|)."""
+    return _relax(prm.u_lb, prm.u_ub) + _relax(prm.w_lb, prm.w_ub)
+
+
 def split_record(rec, N):
     """One instance's dump record -> (step, point, padding): dicts of (stages, width) arrays cut to the horizon,
     and the concatenated entries of the stages beyond it (which the solver must not touch)."""
@@ -69,13 +77,14 @@ def _push(v, lo, hi):
     return min(max(v, lo + pl), hi - pu)
 
 
-def initial_point(ini, N):
+def initial_point(ini, N, prm=kkt.DEFAULT):
     """The iterate of IPM iteration 0 before the multiplier initialisation: x_0 = ini, x_k = 0, u at the bound
     midpoint (bound push 1e-2), bound duals 1 (0 on the fixed stage 0), lam = 0."""
     x = np.zeros((N + 1, NX))
     x[0] = ini
-    x[1:, 10:13] = _push(0.5 * (-kkt.W_UB + kkt.W_UB), W_LO, W_HI)
-    u = np.full((N, NU), _push(0.5 * (0.0 + kkt.U_UB), U_LO, U_HI))
+    u_lo, u_hi, w_lo, w_hi = relaxed_bounds(prm)
+    x[1:, 10:13] = _push(0.5 * (prm.w_lb + prm.w_ub), w_lo, w_hi)
+    u = np.full((N, NU), _push(0.5 * (prm.u_lb + prm.u_ub), u_lo, u_hi))
     zw = np.ones((N + 1, 3))
     zw[0] = 0.0
     return {"x": x, "u": u, "lam": np.zeros((N, NX)), "zLu": np.ones((N, NU)), "zUu": np.ones((N, NU)),
@@ -83,7 +92,7 @@ def initial_point(ini, N):
 
 
 class NewtonSystem:
-    def __init__(self, point, mu, ini, goal, ptra, qtra, t, ulast, N):
+    def __init__(self, point, mu, ini, goal, ptra, qtra, t, ulast, N, prm=kkt.DEFAULT):
         f64 = torch.float64
         self.N, self.n, self.m = N, (NX + NU) * N, NX * N
         self.mu = float(mu)
@@ -97,11 +106,11 @@ class NewtonSystem:
         def J_and_c(v):
             x = torch.cat([x0[None], v[:NX * N].reshape(N, NX)], 0)
             u = v[NX * N:].reshape(N, NU)
-            return kkt.objective_and_defects(x, u, cst[0], cst[1], cst[2], cst[3], tt, ul)
+            return kkt.objective_and_defects(x, u, cst[0], cst[1], cst[2], cst[3], tt, ul, prm)
 
         self._J_and_c = J_and_c
         # objective scaling from the gradient at the initial point
-        p0 = initial_point(np.asarray(ini, dtype=np.float64), N)
+        p0 = initial_point(np.asarray(ini, dtype=np.float64), N, prm)
         g0 = torch.func.grad(lambda v: J_and_c(v)[0])(self._pack(p0["x"], p0["u"]))
         gmax = float(g0.abs().max())
         self.s_obj = max(100.0 / gmax, 1e-8) if gmax > 100.0 else 1.0
@@ -120,13 +129,14 @@ class NewtonSystem:
         self.c = J_and_c(v)[1].reshape(-1).numpy()
         # bounded entries of v: omega of x_1..x_N, every u
         P = self.point
+        u_lo, u_hi, w_lo, w_hi = relaxed_bounds(prm)
         self.sigma = np.zeros(self.n)
         self.gbar = np.zeros(self.n)
         self.zdiff = np.zeros(self.n)       # -z_L + z_U
         iw = (np.arange(1, N + 1)[:, None] - 1) * NX + np.arange(10, 13)[None]
-        for idx, val, zl, zu, lo, hi in ((iw, P["x"][1:, 10:13], P["zLw"][1:], P["zUw"][1:], W_LO, W_HI),
+        for idx, val, zl, zu, lo, hi in ((iw, P["x"][1:, 10:13], P["zLw"][1:], P["zUw"][1:], w_lo, w_hi),
                                          (NX * N + np.arange(NU * N).reshape(N, NU), P["u"], P["zLu"], P["zUu"],
-                                          U_LO, U_HI)):
+                                          u_lo, u_hi)):
             self.sigma[idx] = zl / (val - lo) + zu / (hi - val)
             self.gbar[idx] = -self.mu / (val - lo) + self.mu / (hi - val)
             self.zdiff[idx] = -zl + zu

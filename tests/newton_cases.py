@@ -6,11 +6,16 @@ of tests/newton.py.  A `backend` is a function
 
 that solves the samples `idx` of `prob` with horizon N and max_iter = k + 1 (the solve stops after iteration k) with
 the dump of iteration k and the trace armed.
+
+Every helper takes an optional `prm` (kkt.Problem); None is the reference's problem, as before.  `prob` carries the
+set it was made for under "prm" (absent: the reference's), so a backend reads the parameters from the problem it is
+handed.
 """
 from __future__ import annotations
 
 import numpy as np
 
+import kkt
 import newton
 
 DT = 0.1
@@ -19,16 +24,28 @@ HORIZONS = (50, 1, 2, 3, 7)
 SENTINEL = -777.25        # fill of the dump buffers: entries the solver does not write keep it
 
 
-def problem(batch, N):
-    """Samples 0..3 of scenario.synthetic_batch(64, seed=2025): at N = 50 with their own t, at the short horizons
-    with t = 0.5 N dt (the traversal weight inside the horizon); u_last = 1 on the odd samples, 0 (none) on the even."""
+def _prm(prm):
+    return kkt.DEFAULT if prm is None else prm
+
+
+def oracle_params(prm=None, **kw):
+    """The oracle's parameter block for the set `prm` (None: the defaults) with the solver fields `kw`."""
     from oracle import oracle as O
-    i = np.array(SAMPLES)
+    return O.default_params(**{**({} if prm is None else prm.fields()), **kw})
+
+
+def problem(batch, N, prm=None, t_scale=1.0, samples=SAMPLES):
+    """Samples 0..3 of scenario.synthetic_batch(64, seed=2025): at N = 50 with t_scale times their own t (1 for the
+    reference's 5 s horizon), at the short horizons with t = 0.5 N dt (the traversal weight inside the horizon);
+    u_last = 1 on the odd samples, 0 (none) on the even."""
+    from oracle import oracle as O
+    i = np.array(samples)
+    dt = DT if prm is None else prm.dt
     d = batch["dnn_out"][i].astype(np.float64)
     ul = np.zeros((len(i), 4))
     ul[i % 2 == 1] = 1.0
-    t = d[:, 6].copy() if N == 50 else np.full(len(i), 0.5 * N * DT)
-    return {"ini": batch["ini"][i], "goal": batch["goal"][i], "p": d[:, :3], "a": d[:, 3:6],
+    t = d[:, 6] * t_scale if N == 50 else np.full(len(i), 0.5 * N * dt)
+    return {"prm": prm, "ini": batch["ini"][i], "goal": batch["goal"][i], "p": d[:, :3], "a": d[:, 3:6],
             "q": np.stack([O.rd2quat(a) for a in d[:, 3:6]]), "t": t, "ulast": ul}
 
 
@@ -41,7 +58,7 @@ def oracle_run(prob, N, k, after_refine, idx):
     O.debug_trace(tr, k + 1)
     try:
         O.solve(prob["ini"][idx], prob["goal"][idx], prob["p"][idx], prob["q"][idx], prob["t"][idx],
-                ulast=prob["ulast"][idx], params=O.default_params(horizon=N, max_iter=k + 1))
+                ulast=prob["ulast"][idx], params=oracle_params(prob.get("prm"), horizon=N, max_iter=k + 1))
     finally:
         O.debug_dump(None)
         O.debug_trace(None, 0)
@@ -51,7 +68,7 @@ def oracle_run(prob, N, k, after_refine, idx):
 def oracle_full(prob, N):
     from oracle import oracle as O
     return O.solve(prob["ini"], prob["goal"], prob["p"], prob["q"], prob["t"], ulast=prob["ulast"],
-                   params=O.default_params(horizon=N))
+                   params=oracle_params(prob.get("prm"), horizon=N))
 
 
 def dump_iterations(N, iters):
@@ -94,7 +111,7 @@ def system(tag, prob, N, s, k, case):
     if key not in _systems:
         ul = prob["ulast"][s] if np.any(prob["ulast"][s]) else None
         _systems[key] = newton.NewtonSystem(case["point"], case["trace"][k, 0], prob["ini"][s], prob["goal"][s],
-                                            prob["p"][s], prob["q"][s], prob["t"][s], ul, N)
+                                            prob["p"][s], prob["q"][s], prob["t"][s], ul, N, _prm(prob.get("prm")))
     return _systems[key]
 
 
@@ -147,7 +164,7 @@ def structure(prob, N, cases):
                 assert np.all(np.isfinite(c[side][f])) and not np.any(c[side][f] == SENTINEL), (N, s, k, side, f)
         assert np.all(c["pad"] == SENTINEL), (N, s, k, "padding beyond the horizon written")
         if k == 0:
-            p0 = newton.initial_point(prob["ini"][s], N)
+            p0 = newton.initial_point(prob["ini"][s], N, _prm(prob.get("prm")))
             for f in p0:
                 if f != "lam":   # lam of iteration 0 is the least-squares initialisation
                     assert np.array_equal(c["point"][f], p0[f]), (N, s, k, f)

@@ -40,12 +40,51 @@ with linear_solve accepting a factorisation whose Quu is not positive definite, 
 "delta_w == 0 on 68, > 0 on 0, left out 13" and fails both on the missing second verdict and on the 10 % cap (the 13
 cases whose K(0) has the wrong eigenvalue count are all numerically singular, ratio below 1e-10: the zero quaternion of
 the early iterates; without the cap the leave-out rule would have swallowed them).
+
+The generic parameter set (test_set_*, generic_params.py: Engine(horizon=N, **GENERIC), the dense system built from
+the same parameters).  At the reference's constants Jx == Jy makes Model::az zero, and with it the two Jw row-2 slots
+of the G table, StageHess::wxy and the az terms of A_times / At_times; wqf == 0 removes the goal-attitude block of the
+stage Hessian: every test above factorises systems in which those entries are identically zero, so a slot swapped,
+dropped or read from a neighbour passes them.  Same cases, same six checks, same margins.  First run (MI355X):
+
+    largest residual ratio     unrefined step               refined step
+    N     cases                GPU         oracle           GPU         oracle
+    50    20                   4.700e-11   5.414e-11        8.305e-13   1.452e-11
+    1     12                   1.262e-16   5.545e-17        4.308e-17   4.308e-17
+    2     12                   2.890e-16   2.890e-16        1.640e-16   1.454e-16
+    3     12                   5.445e-15   3.197e-15        3.916e-16   3.737e-16
+    7     12                   4.771e-16   1.887e-16        1.441e-16   1.712e-16
+    inertia: 68 cases, delta_w == 0 on 54, > 0 on 14, none left out
+    least-squares multipliers, GPU / oracle: N = 50: 0 / 0 (cut at 1e3), N = 3: 4.767e-16 / 4.767e-16,
+        N = 7: 2.755e-15 / 2.755e-15
+    point parity: 63 of 68 cases on the oracle's path, all 40 with k <= 1 among them
+
+Mutation check at this set (builds not kept; each run once on test_gpu_newton.py, test_gpu_parity.py,
+test_gpu_generic.py and test_gpu_generic_sens.py).  No test at the default set failed under any of the three: not one
+of this file's 16 default cases, none of test_gpu_parity.py's.
+  (a) M.az replaced by 0 in riccati.inc's Jw (the G table).  test_set_step_solves_the_dense_system fails at N = 50, 2,
+      3 and 7: the unrefined ratio rises to 1.9e-05 at N = 50 (1e-5 cap) and the refined one to 3.7e-11 .. 9.2e-11 at
+      N = 2, 3, 7 against the oracle's 1.5e-16 .. 3.7e-16 (MARGIN); N = 1 passes (one stage: no rate has moved yet).
+      test_set_lsq_multipliers fails at N = 3 and 7 (deviation 4.3e-06 and 2.5e-06 against 4.8e-16 and 2.8e-15: that
+      solve is not refined), test_set_point_parity at iteration 0.  Beyond this file: the solve of sample 0 at N = 50
+      ends with status 6, both sol_gradient modes, the PMP costates and all four finite-difference comparisons fail
+      (err - 10 e up to 1.4e-01).
+  (b) the wqf term removed from the Hxx table (riccati.inc, `M.wqf != 0.0`).  test_set_step_solves_the_dense_system
+      fails at all five horizons (unrefined ratio 5.5e-05 at N = 50, 2.1e-03 at N = 1), test_set_point_parity at
+      iteration 1; the four finite-difference comparisons of test_gpu_generic_sens.py fail (err - 10 e 5.6e-03 ..
+      1.5e-02).  The solve-parity test does not see it: the residual and the refinement read the exact Hessian, so the
+      iterates still converge to the same optimum along the same path.
+  (c) umid = 0.5 * prm.u_ub in ipm_kernel.hip.  test_set_dump_structure fails at every horizon (iteration 0 is not
+      at newton.initial_point's u), test_set_lsq_multipliers at N = 3 and 7 (6.7e-04, 4.6e-04), test_set_point_parity
+      at iteration 0; test_gpu_generic.py's iteration-0 NLP inputs (J off by 3.4e-04 relative), solve parity (cost off
+      by 1.1e-03 at N = 50) and both sol_gradient modes fail.
 """
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")   # tests/newton.py needs it
 
+import generic_params as GP  # noqa: E402
 import newton  # noqa: E402
 import newton_cases as NC  # noqa: E402
 
@@ -54,6 +93,7 @@ pytestmark = pytest.mark.gpu
 MARGIN = 10.0      # GPU against oracle, largest residual ratio over the cases: a different summation order (MFMA
                    # k-steps, FMA contraction, the rsq-based pivot) shifts rounding by small factors; a wrong matrix
                    # entry leaves the ratio orders of magnitude higher
+OTHER_SETS = tuple(n for n in GP.SETS if n != "default")   # the tests below keep their names at the default set
 _cache = {}
 _engines = {}
 
@@ -66,15 +106,15 @@ def batch():
     return S.synthetic_batch(64, seed=2025)
 
 
-def engine(N):
-    if N not in _engines:
+def engine(N, prm=None):
+    if (N, prm) not in _engines:
         from learningagileflight_se3_amd.engine import Engine
-        _engines[N] = Engine(horizon=N)
-    return _engines[N]
+        _engines[(N, prm)] = Engine(horizon=N, **({} if prm is None else prm.fields()))
+    return _engines[(N, prm)]
 
 
 def gpu_solve(prob, N, idx, max_iter):
-    e = engine(N)
+    e = engine(N, prob["prm"])
     p = e.params
     saved = p.max_iter
     p.max_iter = max_iter
@@ -90,7 +130,7 @@ def gpu_solve(prob, N, idx, max_iter):
 
 
 def gpu_run(prob, N, k, after_refine, idx):
-    e = engine(N)
+    e = engine(N, prob["prm"])
     idx = np.asarray(idx)
     rec = torch.full((len(idx), newton.DUMP_W), NC.SENTINEL, dtype=torch.float64, device=e.device)
     tr = torch.zeros((len(idx), k + 1, 16), dtype=torch.float64, device=e.device)
@@ -105,29 +145,30 @@ def gpu_run(prob, N, k, after_refine, idx):
     return rec.cpu().numpy(), tr.cpu().numpy(), resto
 
 
-def horizon(batch, N):
-    """(problem, oracle cases, GPU cases) of horizon N; the dumped iterations come from the oracle's full solve."""
-    if N not in _cache:
-        prob = NC.problem(batch, N)
+def horizon(batch, N, pset="default"):
+    """(problem, oracle cases, GPU cases) of horizon N at the named parameter set; the dumped iterations come from the
+    oracle's full solve."""
+    if (pset, N) not in _cache:
+        prob = GP.problem(batch, N, NC.SAMPLES, pset)
         iters = NC.oracle_full(prob, N)["iters"]
-        _cache[N] = (prob, NC.collect(NC.oracle_run, prob, N, iters), NC.collect(gpu_run, prob, N, iters))
-    return _cache[N]
+        _cache[(pset, N)] = (prob, NC.collect(NC.oracle_run, prob, N, iters), NC.collect(gpu_run, prob, N, iters))
+    return _cache[(pset, N)]
 
 
 @pytest.mark.parametrize("N", NC.HORIZONS)
-def test_step_solves_the_dense_system(batch, N):
+def test_step_solves_the_dense_system(batch, N, pset="default"):
     """Items 1 and 2: the refined step has a residual ratio <= 1e-5 in every case, and the largest ratio of the
     refined and of the unrefined steps is at most MARGIN times the oracle's on the same cases."""
-    prob, ocases, gcases = horizon(batch, N)
+    prob, ocases, gcases = horizon(batch, N, pset)
     assert set(ocases) == set(gcases)
     for (s, k), c in gcases.items():
         assert c["resto"] == [0, 0], (N, s, k, "restoration phase entered")
         assert np.all(c["trace"][:k + 1, 0] > 0.0), (N, s, k)
-    g = NC.ratios("gpu", prob, N, gcases)
-    o = NC.ratios("oracle", prob, N, ocases)
+    g = NC.ratios("gpu/" + pset, prob, N, gcases)
+    o = NC.ratios("oracle/" + pset, prob, N, ocases)
     gpre, gpost = max(v[0] for v in g.values()), max(v[1] for v in g.values())
     opre, opost = max(v[0] for v in o.values()), max(v[1] for v in o.values())
-    print(f"N={N}: {len(g)} cases, largest residual ratio unrefined GPU {gpre:.3e} oracle {opre:.3e}, "
+    print(f"{pset} N={N}: {len(g)} cases, largest residual ratio unrefined GPU {gpre:.3e} oracle {opre:.3e}, "
           f"refined GPU {gpost:.3e} oracle {opost:.3e}")
     assert all(v[1] <= 1e-5 for v in g.values()), g           # IPOPT's residual_ratio_singular
     assert gpost <= MARGIN * opost, (gpost, opost)
@@ -135,60 +176,61 @@ def test_step_solves_the_dense_system(batch, N):
 
 
 @pytest.mark.parametrize("N", NC.HORIZONS)
-def test_dump_structure(batch, N):
+def test_dump_structure(batch, N, pset="default"):
     """Item 4: dx of stage 0 exactly 0, padding beyond N untouched, iteration 0 at the stated initial point."""
-    prob, _, gcases = horizon(batch, N)
+    prob, _, gcases = horizon(batch, N, pset)
     NC.structure(prob, N, gcases)
 
 
-def test_inertia_verdicts(batch):
+def test_inertia_verdicts(batch, pset="default"):
     """Item 3: trace delta_w == 0 exactly where the dense K(0) has 13 N negative eigenvalues, and K(delta_w) has them
     where delta_w > 0, and not yet at the retry before the accepted one; both verdicts occur; at most 10 % of the
     cases left out as numerically singular."""
     total = left = zero = pos = 0
     for N in NC.HORIZONS:
-        prob, _, gcases = horizon(batch, N)
-        n, l = NC.inertia("gpu", prob, N, gcases)
+        prob, _, gcases = horizon(batch, N, pset)
+        n, l = NC.inertia("gpu/" + pset, prob, N, gcases)
         total, left = total + n, left + l
         dws = np.array([c["trace"][k, 8] for (s, k), c in gcases.items()])
         zero, pos = zero + int(np.sum(dws == 0)), pos + int(np.sum(dws > 0))
-    print(f"inertia: {total} cases, delta_w == 0 on {zero}, > 0 on {pos}, left out {left}")
+    print(f"{pset} inertia: {total} cases, delta_w == 0 on {zero}, > 0 on {pos}, left out {left}")
     assert zero > 0 and pos > 0
     assert left <= 0.1 * total
 
 
 @pytest.mark.parametrize("N", (50, 3, 7))
-def test_lsq_multipliers(batch, N):
+def test_lsq_multipliers(batch, N, pset="default"):
     """Item 5: a max_iter = 0 solve returns the least-squares initial multipliers (status 2, iters 0); they agree with
     the dense value within MARGIN times the oracle's own deviation.  At N = 50 the value exceeds 1e3 on every sample,
     so all three sides return exactly 0 (constr_mult_init_max); N = 3 and N = 7 compare the values."""
     from oracle import oracle as O
-    prob = NC.problem(batch, N)
+    prob = GP.problem(batch, N, NC.SAMPLES, pset)
+    prm = NC._prm(prob["prm"])
     idx = np.arange(len(NC.SAMPLES))
     g = gpu_solve(prob, N, idx, 0)
     r = O.solve(prob["ini"], prob["goal"], prob["p"], prob["q"], prob["t"], ulast=prob["ulast"],
-                params=O.default_params(horizon=N, max_iter=0))
+                params=NC.oracle_params(prob["prm"], horizon=N, max_iter=0))
     assert np.all(g["status"] == 2) and np.all(g["iters"] == 0)
     assert g["lam"].shape == (len(idx), N, 13)
     gd, od = [], []
     for s in idx:
         ul = prob["ulast"][s] if np.any(prob["ulast"][s]) else None
-        ns = newton.NewtonSystem(newton.initial_point(prob["ini"][s], N), 0.1, prob["ini"][s], prob["goal"][s],
-                                 prob["p"][s], prob["q"][s], prob["t"][s], ul, N)
+        ns = newton.NewtonSystem(newton.initial_point(prob["ini"][s], N, prm), 0.1, prob["ini"][s], prob["goal"][s],
+                                 prob["p"][s], prob["q"][s], prob["t"][s], ul, N, prm)
         dense = ns.lsq_multipliers() / ns.s_obj
         assert np.any(dense != 0.0) == (N != 50)
         gd.append(NC.lam_deviation(g["lam"][s], dense))
         od.append(NC.lam_deviation(r["lam"][s], dense))
-    print(f"N={N}: least-squares multipliers, deviation from the dense value GPU {max(gd):.3e} oracle {max(od):.3e}")
+    print(f"{pset} N={N}: least-squares multipliers, deviation from the dense value GPU {max(gd):.3e} oracle {max(od):.3e}")
     assert max(gd) <= MARGIN * max(od), (gd, od)
 
 
-def test_point_parity(batch):
+def test_point_parity(batch, pset="default"):
     """Item 6: where the GPU and oracle traces agree up to iteration k on alpha, alpha_z (1e-12 relative), delta_w and
     accepted (exactly), the two dumped points agree to 1e-9 relative to each array's largest entry (at least 1)."""
     covered = total = 0
     for N in NC.HORIZONS:
-        prob, ocases, gcases = horizon(batch, N)
+        prob, ocases, gcases = horizon(batch, N, pset)
         for (s, k), gc in gcases.items():
             oc = ocases[(s, k)]
             total += 1
@@ -202,4 +244,36 @@ def test_point_parity(batch):
             for f in oc["point"]:
                 d = np.max(np.abs(gc["point"][f] - oc["point"][f])) / max(1.0, np.max(np.abs(oc["point"][f])))
                 assert d <= 1e-9, (N, s, k, f, d)
-    print(f"point parity: {covered} of {total} cases on the oracle's path")
+    print(f"{pset} point parity: {covered} of {total} cases on the oracle's path")
+
+
+# The same six checks, same assertions and margins, with Engine(horizon=N, **GENERIC) (generic_params.py): Jx != Jy
+# puts non-zero values into the az slots of the G table and into StageHess::wxy, wqf != 0 adds the goal-attitude block
+# to the stage Hessian that the MFMA factorisation reads, and the asymmetric boxes move Sigma and the barrier gradient.
+@pytest.mark.parametrize("pset", OTHER_SETS)
+@pytest.mark.parametrize("N", NC.HORIZONS)
+def test_set_step_solves_the_dense_system(batch, N, pset):
+    test_step_solves_the_dense_system(batch, N, pset)
+
+
+@pytest.mark.parametrize("pset", OTHER_SETS)
+@pytest.mark.parametrize("N", NC.HORIZONS)
+def test_set_dump_structure(batch, N, pset):
+    test_dump_structure(batch, N, pset)
+
+
+@pytest.mark.parametrize("pset", OTHER_SETS)
+def test_set_inertia_verdicts(batch, pset):
+    test_inertia_verdicts(batch, pset)
+
+
+@pytest.mark.parametrize("pset", OTHER_SETS)
+@pytest.mark.parametrize("N", (50, 3, 7))
+def test_set_lsq_multipliers(batch, N, pset):
+    test_lsq_multipliers(batch, N, pset)
+
+
+@pytest.mark.parametrize("pset", OTHER_SETS)
+def test_set_point_parity(batch, pset):
+    test_point_parity(batch, pset)
+
