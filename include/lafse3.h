@@ -11,6 +11,7 @@
  *   lafse3_get_input      replaces run_quad.get_input         quad_policy.py:202-211
  *   lafse3_ocp_sensitivity  ocSolver + dx, du / d(p_tra, a_tra, t)  (the PDP auxiliary system, quad_OC.py:214-306)
  *   lafse3_ocp_sensitivity_ex  the same with ini_state and goal columns and the feedback gain du_0 / dx_0
+ *   lafse3_ocp_sensitivity_w   the same with per-instance cost weights and the columns of the ten weights
  *
  * Every array argument is a DEVICE pointer (HBM; e.g. a torch.cuda tensor's data_ptr()), owned by
  * the caller, row-major, contiguous.  B is the batch size.  N is params.horizon (<= LAFSE3_MAX_N).
@@ -174,6 +175,37 @@ int lafse3_ocp_sensitivity_ex(lafse3_ctx *ctx, int64_t B, const double *ini_stat
                               double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
                               int32_t groups, double *dx, double *du, double *gain, int32_t *sens_status,
                               void *stream);
+
+/* lafse3_ocp_sensitivity_ex with per-instance cost weights and the sensitivities of the optimum to them: the derivative
+ * with respect to the learnable parameters of the cost (the auxvar of the PDP auxiliary system, quad_OC.py:214-306).
+ *   weights B x LAFSE3_NW (device) or NULL: instance b solves the NLP whose ten cost weights are
+ *   weights[b * 10 .. b * 10 + 9], in the order of lafse3_params: wrt wqt wthrust wrf wvf wqf wwf tra_w_peak
+ *   tra_w_decay du_weight; every other field comes from the context's params.  NULL stands for the context's own
+ *   weights in every instance (the row lafse3_params_weights gives).  The values are used as given, with no
+ *   device-side validation: a non-finite weight ends that instance with status 4, and negative weights are the
+ *   caller's business (the inertia correction copes, or the solve reports its status).
+ * A fourth parameter group follows the three of lafse3_ocp_sensitivity_ex, in the same fixed order:
+ *   LAFSE3_SENS_WEIGHTS  the ten weights, in the order above   10 columns
+ * lafse3_sens_columns_w gives P = 7 [THETA] + 13 [INI] + 3 [GOAL] + 10 [WEIGHTS] (LAFSE3_EINVAL for bits outside
+ * the four groups).  The outputs are lafse3_ocp_sensitivity_ex's with that P; the columns of the first three groups
+ * are its columns bit for bit; dx at stage 0 is zero in the weight columns.  With dx == du == gain == NULL the call
+ * is a plain solve with per-instance weights and `groups` is ignored; otherwise groups == 0 or a bit outside the four
+ * groups is LAFSE3_EINVAL.  The cost is linear in nine of the weights, so their dF/dw is the cost gradient at unit
+ * weight; tra_w_decay enters through the stage weights w_k as t does.  A solver launch for lafse3_reserve,
+ * lafse3_last_kernel_ms, the counters and lafse3_check_device; it runs on the caller's stream and leaves the
+ * caller's current device alone.  lafse3_sens_columns and lafse3_ocp_sensitivity_ex keep refusing
+ * LAFSE3_SENS_WEIGHTS. */
+#define LAFSE3_NW 10            /* wrt wqt wthrust wrf wvf wqf wwf tra_w_peak tra_w_decay du_weight (lafse3_params order) */
+#define LAFSE3_SENS_WEIGHTS 8   /* 10 columns, after THETA, INI, GOAL */
+int lafse3_sens_columns_w(int32_t groups);
+/* The ten cost weights of *p in the column order: the row a NULL `weights` stands for. */
+int lafse3_params_weights(const lafse3_params *p, double w[LAFSE3_NW]);
+int lafse3_ocp_sensitivity_w(lafse3_ctx *ctx, int64_t B, const double *ini_state, const double *goal,
+                             const double *p_tra, const double *a_tra, const double *t, const double *u_last,
+                             const double *weights,
+                             double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
+                             int32_t groups, double *dx, double *du, double *gain, int32_t *sens_status,
+                             void *stream);
 
 /* fp32 twin of lafse3_ocp_solve: the same arguments as float32 device buffers.  Inputs are
  * widened to fp64 and outputs rounded to fp32 on the device; the NLP itself is solved in fp64 (IPOPT's

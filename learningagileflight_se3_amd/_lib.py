@@ -22,6 +22,12 @@ SENS_GROUPS = {"theta": 1, "ini": 2, "goal": 4}
 SENS_COLUMNS = {"theta": ("p_tra[0]", "p_tra[1]", "p_tra[2]", "a_tra[0]", "a_tra[1]", "a_tra[2]", "t"),
                 "ini": tuple(f"ini_state[{i}]" for i in range(13)),
                 "goal": ("goal[0]", "goal[1]", "goal[2]")}
+# lafse3_ocp_sensitivity_w: the same groups and a fourth, the ten cost weights (LAFSE3_SENS_WEIGHTS, LAFSE3_NW), whose
+# columns are named as the fields of lafse3_params, in its order
+NW = 10
+WEIGHT_NAMES = ("wrt", "wqt", "wthrust", "wrf", "wvf", "wqf", "wwf", "tra_w_peak", "tra_w_decay", "du_weight")
+SENS_GROUPS_W = {**SENS_GROUPS, "weights": 8}
+SENS_COLUMNS_W = {**SENS_COLUMNS, "weights": WEIGHT_NAMES}
 
 
 class Params(ctypes.Structure):
@@ -66,6 +72,9 @@ SIGNATURES = {
     "lafse3_ocp_sensitivity": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] * 6 + [_vp] * 3 + [_vp]),
     "lafse3_sens_columns": (ctypes.c_int, [_i32]),
     "lafse3_ocp_sensitivity_ex": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] * 6 + [_i32] + [_vp] * 4 + [_vp]),
+    "lafse3_sens_columns_w": (ctypes.c_int, [_i32]),
+    "lafse3_params_weights": (ctypes.c_int, [_P(Params), _P(_d)]),
+    "lafse3_ocp_sensitivity_w": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] + [_vp] * 6 + [_i32] + [_vp] * 4 + [_vp]),
     "lafse3_objective": (ctypes.c_int, [_vp, _i64] + [_vp] * 7 + [_vp, _vp, _vp]),
     "lafse3_sol_gradient": (ctypes.c_int, [_vp, _i64] + [_vp] * 5 + [_vp, _vp, _vp, _vp]),
     "lafse3_get_input": (ctypes.c_int, [_vp, _i64] + [_vp] * 4 + [_vp, _vp, _vp, _vp]),

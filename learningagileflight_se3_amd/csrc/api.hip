@@ -3,6 +3,7 @@
 // Host side only: argument checking, workspace management, kernel launches on the caller's stream.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
@@ -330,7 +331,8 @@ __global__ void slots_init_kernel(double *R, int32_t *S, int64_t n)
 }
 
 static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t sched_samples = 0,
-                  const lafse3::SensArgs *sens = nullptr, const lafse3::SensExArgs *sensx = nullptr)
+                  const lafse3::SensArgs *sens = nullptr, const lafse3::SensExArgs *sensx = nullptr,
+                  const lafse3::SensWArgs *sensw = nullptr)
 {
     if (A.n_inst == 0) return LAFSE3_OK;
     // trajectory scoring (MODE_REWARD) counts nothing and has its own queue head: it leaves the last solver
@@ -388,6 +390,7 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
     // and so are the extra stores of a debug dump that carries the iterate (ipm_kernel_dump: plain solves only)
     if (sens) hipLaunchKernelGGL(lafse3::ipm_kernel_sens, dim3((unsigned)grid), dim3(64), 0, st, A, *sens);
     else if (sensx) hipLaunchKernelGGL(lafse3::ipm_kernel_sens_ex, dim3((unsigned)grid), dim3(64), 0, st, A, *sensx);
+    else if (sensw) hipLaunchKernelGGL(lafse3::ipm_kernel_sens_w, dim3((unsigned)grid), dim3(64), 0, st, A, *sensw);
     else if (A.dump && A.mode == lafse3::MODE_SOLVE && !A.sched)
         hipLaunchKernelGGL(lafse3::ipm_kernel_dump, dim3((unsigned)grid), dim3(64), 0, st, A);
     else hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
@@ -405,12 +408,12 @@ static lafse3::KernelArgs blank_args()
     return A;
 }
 
-// lafse3_ocp_solve and, with sens or sensx, lafse3_ocp_sensitivity / _ex: the one place that fills the MODE_SOLVE
-// arguments
+// lafse3_ocp_solve and, with sens, sensx or sensw, lafse3_ocp_sensitivity / _ex / _w: the one place that fills the
+// MODE_SOLVE arguments
 static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
                  const double *a_tra, const double *t, const double *u_last, double *x, double *u, double *lam,
                  double *cost, int32_t *status, int32_t *iters, void *stream, const lafse3::SensArgs *sens,
-                 const lafse3::SensExArgs *sensx = nullptr)
+                 const lafse3::SensExArgs *sensx = nullptr, const lafse3::SensWArgs *sensw = nullptr)
 {
     if (const int rc = check_call(c, B, {ini, goal, p_tra, a_tra, t})) return rc;
     if (B == 0) return LAFSE3_OK;
@@ -421,7 +424,7 @@ static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal
     A.n_inst = B;
     A.ini = ini; A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;
     A.x_out = x; A.u_out = u; A.lam_out = lam; A.cost_out = cost; A.status_out = status; A.iters_out = iters;
-    return launch(c, A, (hipStream_t)stream, 0, sens, sensx);
+    return launch(c, A, (hipStream_t)stream, 0, sens, sensx, sensw);
 }
 
 int lafse3_ocp_solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
@@ -468,6 +471,48 @@ int lafse3_ocp_sensitivity_ex(lafse3_ctx *c, int64_t B, const double *ini, const
     lafse3::SensExArgs Z;
     Z.dx_out = dx; Z.du_out = du; Z.gain_out = gain; Z.sens_out = sens_status; Z.groups = groups;
     return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr, &Z);
+}
+
+static_assert(LAFSE3_SENS_WEIGHTS == lafse3::SENS_G_W && LAFSE3_NW == lafse3::NW,
+              "sens_w.inc reads the header's weights group");
+// the ten weights are contiguous doubles of lafse3_params in the column order (weight_columns.hpp)
+static_assert(offsetof(lafse3_params, du_weight) - offsetof(lafse3_params, wrt) == (LAFSE3_NW - 1) * sizeof(double) &&
+              offsetof(lafse3_params, tra_w_peak) - offsetof(lafse3_params, wrt) == lafse3::W_PEAK * sizeof(double),
+              "lafse3_params: wrt .. du_weight are LAFSE3_NW contiguous doubles");
+
+int lafse3_sens_columns_w(int32_t groups)
+{
+    if (groups & ~lafse3::SENS_W_ALL)
+        return fail(LAFSE3_EINVAL, "lafse3_sens_columns_w: bits outside LAFSE3_SENS_THETA | _INI | _GOAL | _WEIGHTS");
+    return lafse3::sens_w_columns(groups);
+}
+
+int lafse3_params_weights(const lafse3_params *p, double w[LAFSE3_NW])
+{
+    if (!p || !w) return fail(LAFSE3_EINVAL, "null argument");
+    std::memcpy(w, &p->wrt, LAFSE3_NW * sizeof(double));
+    return LAFSE3_OK;
+}
+
+int lafse3_ocp_sensitivity_w(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
+                             const double *a_tra, const double *t, const double *u_last, const double *weights,
+                             double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
+                             int32_t groups, double *dx, double *du, double *gain, int32_t *sens_status, void *stream)
+{
+    if (!c) return fail(LAFSE3_EINVAL, "bad ctx / batch");
+    const bool sens = dx || du || gain;
+    // without dx, du, gain and weights the call is lafse3_ocp_solve
+    if (!sens && !weights)
+        return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr);
+    if (sens && (groups == 0 || (groups & ~lafse3::SENS_W_ALL)))
+        return fail(LAFSE3_EINVAL, "lafse3_ocp_sensitivity_w: groups must be a non-empty subset of "
+                                   "LAFSE3_SENS_THETA | LAFSE3_SENS_INI | LAFSE3_SENS_GOAL | LAFSE3_SENS_WEIGHTS");
+    lafse3::SensWArgs Z;
+    Z.weights = weights;
+    Z.dx_out = dx; Z.du_out = du; Z.gain_out = gain; Z.sens_out = sens_status;
+    Z.groups = sens ? groups : 0;   // a plain solve with per-instance weights ignores groups
+    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr, nullptr,
+                 &Z);
 }
 
 // ---- fp32 twin of lafse3_ocp_solve: float inputs/outputs at the boundary, fp64 arithmetic inside (IPOPT's
@@ -752,6 +797,6 @@ int lafse3_record_iters(lafse3_ctx *c, int32_t *buf, int64_t capacity)
 
 const char *lafse3_last_error(void) { return g_err.c_str(); }
 
-const char *lafse3_version(void) { return "lafse3 0.6.0 (gfx950)"; }
+const char *lafse3_version(void) { return "lafse3 0.7.0 (gfx950)"; }
 
 }  // extern "C"

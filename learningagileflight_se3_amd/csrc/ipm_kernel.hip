@@ -20,6 +20,7 @@
 
 #include "lafse3.h"
 #include "model.hpp"
+#include "weight_columns.hpp"
 #include "riccati_tables.hpp"
 
 namespace lafse3 {
@@ -173,6 +174,14 @@ struct SensExArgs {
     double *gain_out;               // B x 4 x P (nullable)
     int32_t *sens_out;              // as SensArgs::sens_out
     int32_t groups;                 // LAFSE3_SENS_THETA | _INI | _GOAL
+};
+// second argument of ipm_kernel_sens_w (sens_w.inc): SensExArgs with the weights group and the per-instance weights
+struct SensWArgs {
+    const double *weights;          // B x LAFSE3_NW cost weights, lafse3_params order (nullable: the context's)
+    double *dx_out, *du_out;        // B x P x (N+1) x 13, B x P x N x 4 (each nullable)
+    double *gain_out;               // B x 4 x P (nullable)
+    int32_t *sens_out;              // as SensArgs::sens_out
+    int32_t groups;                 // LAFSE3_SENS_THETA | _INI | _GOAL | _WEIGHTS
 };
 
 struct Ctl {
@@ -1831,6 +1840,7 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 
 #include "sens.inc"
 #include "sens_ex.inc"
+#include "sens_w.inc"
 
 // ------------------------------------------------------------------------------------------------
 // waves per SIMD the register allocation targets (LDS admits 2: Smem <= 20 KB)
@@ -1839,15 +1849,36 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 // SENS (ipm_kernel_sens): the sensitivity pass of sens.inc follows a MODE_SOLVE instance; ipm_kernel compiles none of it.
 // DUMP (ipm_kernel_dump): the debug dump also records the iterate (dump_point); ipm_kernel compiles none of that.
 // SENSX (ipm_kernel_sens_ex): the pass of sens_ex.inc follows a MODE_SOLVE instance, as SENS.
-template <bool SENS, bool DUMP = false, bool SENSX = false>
+// SENSW (ipm_kernel_sens_w): the instance's ten cost weights come from ZW->weights (MODE_SOLVE only) and the pass of
+// sens_w.inc follows.
+template <bool SENS, bool DUMP = false, bool SENSX = false, bool SENSW = false>
 __device__ __attribute__((always_inline)) inline int run_instance(const KernelArgs &A, Smem &S, const int64_t inst,
                                                                  gdouble *ws, const SensArgs *Z = nullptr,
-                                                                 const SensExArgs *ZX = nullptr)
+                                                                 const SensExArgs *ZX = nullptr,
+                                                                 const SensWArgs *ZW = nullptr)
 {
     const int lane = lane_id();
     const lafse3_params &prm = A.prm;
     Model &M = S.mdl;
     M = make_model(prm);   // every lane writes the same values: no barrier needed before its own reads
+    // SENSW: the traversal weight's shape of this instance (the other kernels read the context's where they use it)
+    [[maybe_unused]] double w_peak = 0.0, w_decay = 0.0;
+    // a non-finite weight need not reach the error norms (fmax drops a NaN): the instance ends as non-finite below
+    [[maybe_unused]] bool w_nonfinite = false;
+    if constexpr (SENSW) {
+        w_peak = prm.tra_w_peak;
+        w_decay = prm.tra_w_decay;
+        if (ZW->weights) {
+            // used as given (include/lafse3.h): everything downstream reads M and S.wk
+            const double *w = ZW->weights + inst * (int64_t)NW;
+            M.wrt = w[W_WRT]; M.wqt = w[W_WQT]; M.wthrust = w[W_WTHRUST]; M.wrf = w[W_WRF]; M.wvf = w[W_WVF];
+            M.wqf = w[W_WQF]; M.wwf = w[W_WWF]; M.du_w = w[W_DU];
+            w_peak = w[W_PEAK];
+            w_decay = w[W_DECAY];
+#pragma unroll
+            for (int q = 0; q < NW; ++q) w_nonfinite |= !isfinite(w[q]);
+        }
+    }
     const int N = prm.horizon;
     WS_TRAJ(ws);
     gdouble *FT = ws + WS_FILT, *FP = ws + WS_FILT + FMAX;
@@ -1987,7 +2018,8 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
                 ZUW[c * SX + k] = (k >= 1) ? 1.0 : 0.0;
             }
             double dtk = prm.dt * k - tt;
-            S.wk[k] = prm.tra_w_peak * exp(-prm.tra_w_decay * dtk * dtk);
+            if constexpr (SENSW) S.wk[k] = w_peak * exp(-w_decay * dtk * dtk);   // the same expression: the same bits
+            else S.wk[k] = prm.tra_w_peak * exp(-prm.tra_w_decay * dtk * dtk);
         }
         if (lane < N) {
             const int k = lane;
@@ -2089,6 +2121,8 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
         PT_END(S, 1);
         double e0 = err_value(E, 0);
         if (!isfinite(e0)) { status = ST_NONFINITE; break; }
+        if constexpr (SENSW)
+            if (w_nonfinite) { status = ST_NONFINITE; break; }
         if (e0 <= prm.tol && E.dinf / C.s <= 1.0 && E.pinf <= 1e-4 && E.c0 / C.s <= 1e-4) {
             status = ST_SOLVED;
             break;
@@ -2503,6 +2537,16 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
             if (lane == 0 && ZX->sens_out) ZX->sens_out[inst] = sst;
         }
     }
+    if constexpr (SENSW) {
+        if (A.mode == MODE_SOLVE && (ZW->dx_out || ZW->du_out || ZW->gain_out)) {
+            const int64_t P = sens_w_columns(ZW->groups);
+            const int sst = sens_w_pass(prm, M, S, C, ws, a3, tt, w_decay, status <= 1, ZW->groups,
+                                        ZW->dx_out ? ZW->dx_out + inst * P * (N + 1) * NX : nullptr,
+                                        ZW->du_out ? ZW->du_out + inst * P * N * NU : nullptr,
+                                        ZW->gain_out ? ZW->gain_out + inst * NU * P : nullptr);
+            if (lane == 0 && ZW->sens_out) ZW->sens_out[inst] = sst;
+        }
+    }
     PT_END(S, 10);
 #ifdef LAFSE3_PHASE_TIMERS
     if (A.ptime && lane < 16) A.ptime[inst * PT_COLS + lane] = S.pt[lane];
@@ -2727,6 +2771,24 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_sens_ex(KernelArgs A, SensEx
         KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         __asm__ volatile("" : "+s"(Ap));
         run_instance<false, false, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, &Z);
+    }
+}
+
+// The persistent solver with per-instance cost weights and the pass of sens_w.inc compiled in
+// (lafse3_ocp_sensitivity_w only): as ipm_kernel_sens_ex a further instantiation of run_instance in a kernel of its own.
+__global__ __launch_bounds__(64, 1) void ipm_kernel_sens_w(KernelArgs A, SensWArgs Z)
+{
+    Smem &S = instance_smem();
+    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
+    for (;;) {
+        unsigned long long v = 0ull;
+        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
+        const int64_t inst = bcast_i64((int64_t)v);
+        if (inst >= A.n_inst) break;
+        typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
+        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+        __asm__ volatile("" : "+s"(Ap));
+        run_instance<false, false, false, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, nullptr, &Z);
     }
 }
 

@@ -15,6 +15,10 @@ When ``ini_state`` or ``goal`` requires a gradient, ``mpc_layer`` goes through `
 which also has their columns, and ``mpc_policy`` returns the first control u*_0 with a gradient to all five inputs from
 the feedback gain alone (include/lafse3.h lafse3_ocp_sensitivity_ex): the layer for closed-loop rollouts.  u_last is
 a constant throughout.
+
+With ``weights=`` (the ten cost weights per instance, ``Engine.ocp_sensitivity_w``) both layers solve each instance
+under its own weights and send a gradient to them: the derivative with respect to the learnable parameters of the
+cost.  Without it they are the functions above, with the same launches.
 """
 from __future__ import annotations
 
@@ -78,21 +82,26 @@ class MPCFunction(torch.autograd.Function):
 _GROUPS = (("theta", 7, ((2, 0, 3), (3, 3, 6), (4, 6, 7))), ("ini", 13, ((0, 0, 13),)), ("goal", 3, ((1, 0, 3),)))
 
 
-def _needed_groups(needs):
-    """needs: needs_input_grad of (ini_state, goal, p_tra, a_tra, t) -> the groups with an input that needs one."""
-    return tuple(name for name, _, members in _GROUPS if any(needs[i] for i, _, _ in members))
+# ... and of Engine.ocp_sensitivity_w, whose inputs are (ini_state, goal, p_tra, a_tra, t, weights)
+_GROUPS_W = _GROUPS + (("weights", 10, ((5, 0, 10),)),)
+
+
+def _needed_groups(needs, table=_GROUPS):
+    """needs: needs_input_grad of (ini_state, goal, p_tra, a_tra, t[, weights]) -> the groups with an input that
+    needs one."""
+    return tuple(name for name, _, members in table if any(needs[i] for i, _, _ in members))
 
 
 def _meta(v):
     return (v.dtype, v.shape, v.device) if isinstance(v, torch.Tensor) else None
 
 
-def _scatter_columns(g, groups, metas, needs):
+def _scatter_columns(g, groups, metas, needs, table=_GROUPS):
     """g (B, P): the gradient w.r.t. the P columns of ``groups`` -> the gradients of (ini_state, goal, p_tra, a_tra,
-    t) in their dtype, shape and device; None for an input that is no tensor or needs none."""
-    out = [None] * 5
+    t[, weights]) in their dtype, shape and device; None for an input that is no tensor or needs none."""
+    out = [None] * len(metas)
     col = 0
-    for name, n, members in _GROUPS:
+    for name, n, members in table:
         if name not in groups:
             continue
         for i, lo, hi in members:
@@ -164,19 +173,86 @@ class MPCPolicyFunction(torch.autograd.Function):
         return (None, *_scatter_columns(g, ctx.groups, ctx.metas, ctx.needs_input_grad[1:6]), None)
 
 
+class MPCFunctionW(torch.autograd.Function):
+    """MPCFunctionEx under per-instance cost weights: (engine, ini_state, goal, p_tra, a_tra, t, u_last, weights) ->
+    (x, u, status).  One ``Engine.ocp_sensitivity_w`` launch; ``weights`` is (B, 10) or (10,) (broadcast; its gradient
+    is then summed over the batch) and, like the other five inputs, receives a gradient in its own dtype and shape
+    when it requires one."""
+
+    @staticmethod
+    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights):
+        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
+        ctx.groups = _needed_groups(needs, _GROUPS_W)
+        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t, weights))
+        want = ("x", "u", "dx", "du") if ctx.groups else ("x", "u")
+        out = engine.ocp_sensitivity_w(ini_state, goal, p_tra, a_tra, t, u_last, weights=weights,
+                                       groups=ctx.groups or ("weights",), want=want)
+        if ctx.groups:
+            ctx.save_for_backward(out["dx"], out["du"], out["sens_status"])
+        ctx.mark_non_differentiable(out["status"])
+        return out["x"], out["u"], out["status"]
+
+    @staticmethod
+    def backward(ctx, g_x, g_u, _g_status):
+        dx, du, sens_status = ctx.saved_tensors
+        g = torch.zeros(dx.shape[:2], dtype=dx.dtype, device=dx.device)
+        if g_x is not None:
+            g = g + torch.einsum("bqki,bki->bq", dx, g_x.to(dx.dtype))
+        if g_u is not None:
+            g = g + torch.einsum("bqka,bka->bq", du, g_u.to(du.dtype))
+        g = torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
+        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
+        gr = _scatter_columns(g, ctx.groups, ctx.metas, needs, _GROUPS_W)
+        return (None, *gr[:5], None, gr[5])
+
+
+class MPCPolicyFunctionW(torch.autograd.Function):
+    """MPCPolicyFunction under per-instance cost weights: (engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
+    -> (u0, status), differentiable in the five inputs and the weights through ``gain`` alone."""
+
+    @staticmethod
+    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights):
+        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
+        ctx.groups = _needed_groups(needs, _GROUPS_W)
+        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t, weights))
+        out = engine.ocp_sensitivity_w(ini_state, goal, p_tra, a_tra, t, u_last, weights=weights,
+                                       groups=ctx.groups or ("weights",),
+                                       want=("u", "gain") if ctx.groups else ("u",))
+        if ctx.groups:
+            ctx.save_for_backward(out["gain"], out["sens_status"])
+        ctx.mark_non_differentiable(out["status"])
+        return out["u"][:, 0].contiguous(), out["status"]
+
+    @staticmethod
+    def backward(ctx, g_u0, _g_status):
+        gain, sens_status = ctx.saved_tensors
+        g = torch.einsum("baq,ba->bq", gain, g_u0.to(gain.dtype))
+        g = torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
+        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
+        gr = _scatter_columns(g, ctx.groups, ctx.metas, needs, _GROUPS_W)
+        return (None, *gr[:5], None, gr[5])
+
+
 def _wants_grad(v):
     return isinstance(v, torch.Tensor) and v.requires_grad
 
 
-def mpc_layer(engine, ini_state, goal, p_tra, a_tra, t, u_last=None):
+def mpc_layer(engine, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None):
     """Differentiable batched MPC solve -> (x, u, status); see MPCFunction.  When ini_state or goal is a tensor that
-    requires a gradient, the solve goes through MPCFunctionEx, which also returns gradients to them."""
+    requires a gradient, the solve goes through MPCFunctionEx, which also returns gradients to them.  ``weights``
+    ((B, 10) or (10,), the cost weights of each instance): the solve goes through MPCFunctionW, and a ``weights`` that
+    requires a gradient receives one."""
+    if weights is not None:
+        return MPCFunctionW.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
     if _wants_grad(ini_state) or _wants_grad(goal):
         return MPCFunctionEx.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last)
     return MPCFunction.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last)
 
 
-def mpc_policy(engine, ini_state, goal, p_tra, a_tra, t, u_last=None):
+def mpc_policy(engine, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None):
     """The MPC policy u0 = u*_0(ini_state, goal, p_tra, a_tra, t) -> (u0 (B, 4), status), differentiable in all five
-    (see MPCPolicyFunction): the layer for closed-loop rollouts x_{t+1} = plant(x_t, u0(x_t, ..))."""
+    (see MPCPolicyFunction): the layer for closed-loop rollouts x_{t+1} = plant(x_t, u0(x_t, ..)).  ``weights`` as in
+    mpc_layer (MPCPolicyFunctionW)."""
+    if weights is not None:
+        return MPCPolicyFunctionW.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
     return MPCPolicyFunction.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last)

@@ -11,6 +11,7 @@ Reference interfaces mirrored (yanrui89/LearningAgileFlight_SE3):
   Engine.get_input     run_quad.get_input      quad_policy.py:202-211
   Engine.ocp_sensitivity  ocSolver + dx*/dtheta, du*/dtheta (the PDP auxiliary system sketched in quad_OC.py:214-306)
   Engine.ocp_sensitivity_ex  the same with ini_state and goal columns and the MPC feedback gain du*_0/dx_0
+  Engine.ocp_sensitivity_w   the same with per-instance cost weights and the columns of the ten weights
 """
 from __future__ import annotations
 
@@ -322,6 +323,69 @@ class Engine:
                                                 _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["gain"]),
                                                 _ptr(out.get("sens_status")), self._stream()),
               "lafse3_ocp_sensitivity_ex")
+        res = {k: v for k, v in out.items() if v is not None}
+        res["columns"] = columns
+        return res
+
+    def weights(self):
+        """The context's ten cost weights (_lib.WEIGHT_NAMES order) as a (10,) float64 device tensor: the row a
+        ``weights=None`` stands for (lafse3_params_weights)."""
+        w = (ctypes.c_double * _lib.NW)()
+        check(self._L.lafse3_params_weights(ctypes.byref(self.params), w), "lafse3_params_weights")
+        return torch.tensor(list(w), dtype=torch.float64, device=self.device)
+
+    def ocp_sensitivity_w(self, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None,
+                          groups=("theta", "ini", "goal", "weights"), want=("x", "u", "dx", "du", "gain")):
+        """ocp_sensitivity_ex with per-instance cost weights and the sensitivities to them
+        (lafse3_ocp_sensitivity_w), one launch.
+
+        ``weights``: (B, 10) or (10,) (broadcast over the batch), the ten cost weights in _lib.WEIGHT_NAMES order
+        (wrt wqt wthrust wrf wvf wqf wwf tra_w_peak tra_w_decay du_weight); instance b solves the NLP with row b,
+        every other parameter is the context's.  None: the context's weights.  They are used as given.
+        ``groups``: as ocp_sensitivity_ex plus "weights" (10 columns, last).  Returns ocp_sensitivity_ex's dict;
+        ``columns`` ends with the ten weight names.  Without dx, du and gain in ``want`` the call is a plain solve
+        with those weights.  float64 only."""
+        G = _lib.SENS_GROUPS_W
+        if isinstance(groups, str):
+            groups = (groups,)
+        if isinstance(groups, int):
+            mask = int(groups)
+        else:
+            unknown = [g for g in groups if g not in G]
+            if unknown:
+                raise ValueError(f"groups: unknown {unknown}; expected any of {list(G)}")
+            mask = sum(bit for g, bit in G.items() if g in groups)
+        sens = any(k in want for k in ("dx", "du", "gain"))
+        if sens and (mask == 0 or mask & ~sum(G.values())):
+            raise ValueError(f"groups: {groups!r} selects no column or a bit outside {G}")
+        columns = [c for g, bit in G.items() if mask & bit for c in _lib.SENS_COLUMNS_W[g]]
+        P = len(columns)
+        d, f64 = self.device, torch.float64
+        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
+        w = None
+        if weights is not None:
+            w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights))
+            w = w.detach().to(device=d, dtype=f64)
+            given = tuple(w.shape)
+            if given == (_lib.NW,):
+                w = w.unsqueeze(0).expand(B, _lib.NW)
+            if tuple(w.shape) != (B, _lib.NW):
+                raise ValueError(f"weights: expected ({B}, {_lib.NW}) or ({_lib.NW},), got {given}")
+            w = w.contiguous()
+        N = self.horizon
+        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,),
+                  "dx": (B, P, N + 1, NX), "du": (B, P, N, NU), "gain": (B, NU, P)}
+        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
+        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
+        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
+        if sens:   # without dx, du and gain the call is a plain solve
+            out["sens_status"] = torch.empty((B,), dtype=torch.int32, device=d)
+        check(self._L.lafse3_ocp_sensitivity_w(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt),
+                                               _ptr(ul), _ptr(w), _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]),
+                                               _ptr(out["cost"]), _ptr(out["status"]), _ptr(out["iters"]), mask,
+                                               _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["gain"]),
+                                               _ptr(out.get("sens_status")), self._stream()),
+              "lafse3_ocp_sensitivity_w")
         res = {k: v for k, v in out.items() if v is not None}
         res["columns"] = columns
         return res
