@@ -311,9 +311,29 @@ int lafse3_debug_trace(lafse3_ctx *ctx, double *buf, int iters);
  * (stage 0, which is fixed, has zLw = zUw = 0).  mu and delta_w of that iteration are words 0 and 8 of
  * lafse3_debug_trace.  With an inertia retry the pre-refinement record is that of the last retry.
  * The iterate is written by lafse3_ocp_solve / lafse3_ocp_solve_f32 launches, which run a kernel of their own while
- * a dump is armed (the extra stores are compiled out of the production kernel); the other entry points write the step
- * only, at the same stride of 3732 doubles per instance.  buf = NULL disables. */
+ * a dump (this one or lafse3_debug_dump_resto) is armed (the extra stores are compiled out of the production kernel); the
+ * other entry points write the step only, at the same stride of 3732 doubles per instance.  buf = NULL disables. */
 int lafse3_debug_dump(lafse3_ctx *ctx, double *buf, int it, int after_refine);
+/* Debug: dump one Newton step of the restoration phase (resto.inc) into buf (instances x 9153): iteration `it` of the
+ * entry-th entry into the phase of each solve, both 0-based (an instance that never gets there writes nothing).  One
+ * record per instance, every array stage-major and padded to LAFSE3_MAX_N stages (entries of stages beyond the horizon
+ * are not written), in this order:
+ *   the step       dx (51x13) | du (50x4) | lam+ (50x13) | dp (50x13) | dn (50x13)                     2813 doubles
+ *                  before (after_refine = 0) or after the iterative refinement; with an inertia retry, of the last retry
+ *   the iterate    x (51x13) | u (50x4) | lam (50x13) | zLu (50x4) | zUu (50x4) | zLw (51x3) | zUw (51x3) |
+ *                  p (50x13) | n (50x13) | z_p (50x13) | z_n (50x13)                                    4819 doubles
+ *                  the point the system was formed at; row k of p, n, z_p, z_n belongs to the constraint
+ *                  f_d(x_k, u_k) - x_{k+1} - p_k + n_k = 0, whose multiplier is lam_k (L = f_R + lam^T c_R)
+ *   the reference  x_R (51x13) | u_R (50x4)          the point where the phase started                  863 doubles
+ *   scalars        mu | eta | delta_w of the dumped factorisation | written (1.0 once the step is there) |
+ *                  residual ratio before the refinement | after it                                        6 doubles
+ *   least squares  lam+ (50x13) of the multiplier estimate at the start point, before the cut at 1e3 |
+ *                  ok (1: factorised, 0: wrong inertia, lam+ not written) | IPM iterations taken before this
+ *                  entry (iteration `it` of the entry is IPM iteration that + it)                        652 doubles
+ * The least-squares part is written at the entry itself, whatever `it`.  Written by lafse3_ocp_solve /
+ * lafse3_ocp_solve_f32 launches only, which run the kernel of lafse3_debug_dump while either dump is armed (the stores
+ * are compiled out of the production kernels); both dumps may be armed together.  buf = NULL disables. */
+int lafse3_debug_dump_resto(lafse3_ctx *ctx, double *buf, int entry, int it, int after_refine);
 /* Debug: per-instance record of 32 x uint64 into buf (instances x 32).  The timer build (-DLAFSE3_PHASE_TIMERS)
  * fills columns 0..15 and 24..31, every build the placement record 16..23: 12 phase timers in s_memtime cycles (init, errors, table, backward, forward, adjoint, residual, refine-backward,
  * line search, accept, reward, other), 4 backward-sweep stage-phase timers, then the placement record: start and

@@ -85,6 +85,7 @@ SIGNATURES = {
     "lafse3_last_counters": (ctypes.c_int, [_vp, _P(_i64)]),
     "lafse3_debug_trace": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "lafse3_debug_dump": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int]),
+    "lafse3_debug_dump_resto": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "lafse3_debug_timers": (ctypes.c_int, [_vp, _vp]),
     "lafse3_record_iters": (ctypes.c_int, [_vp, _vp, _i64]),
     "lafse3_check_device": (ctypes.c_int, [_vp]),

@@ -102,6 +102,7 @@ struct lafse3_ctx {
     int trace_iters = 0;
     double *dump = nullptr;
     int dump_it = -1, dump_refine = 0;
+    lafse3::RestoDumpArgs rdump = {nullptr, -1, -1, 0};
     unsigned long long *ptime = nullptr;
     int32_t *iters_rec = nullptr;        // lafse3_record_iters target (device)
     int64_t iters_cap = 0;               // its capacity in entries
@@ -391,8 +392,8 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
     if (sens) hipLaunchKernelGGL(lafse3::ipm_kernel_sens, dim3((unsigned)grid), dim3(64), 0, st, A, *sens);
     else if (sensx) hipLaunchKernelGGL(lafse3::ipm_kernel_sens_ex, dim3((unsigned)grid), dim3(64), 0, st, A, *sensx);
     else if (sensw) hipLaunchKernelGGL(lafse3::ipm_kernel_sens_w, dim3((unsigned)grid), dim3(64), 0, st, A, *sensw);
-    else if (A.dump && A.mode == lafse3::MODE_SOLVE && !A.sched)
-        hipLaunchKernelGGL(lafse3::ipm_kernel_dump, dim3((unsigned)grid), dim3(64), 0, st, A);
+    else if ((A.dump || c->rdump.buf) && A.mode == lafse3::MODE_SOLVE && !A.sched)
+        hipLaunchKernelGGL(lafse3::ipm_kernel_dump, dim3((unsigned)grid), dim3(64), 0, st, A, c->rdump);
     else hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
     e = hipGetLastError();
     (void)hipEventRecord(c->ev1, st);
@@ -783,6 +784,17 @@ int lafse3_debug_dump(lafse3_ctx *c, double *buf, int it, int after_refine)
     c->dump = buf;
     c->dump_it = buf ? it : -1;
     c->dump_refine = after_refine;
+    return LAFSE3_OK;
+}
+
+int lafse3_debug_dump_resto(lafse3_ctx *c, double *buf, int entry, int it, int after_refine)
+{
+    if (!c) return fail(LAFSE3_EINVAL, "null ctx");
+    if (buf && (entry < 0 || it < 0)) return fail(LAFSE3_EINVAL, "debug_dump_resto: entry and it must be >= 0");
+    c->rdump.buf = buf;
+    c->rdump.entry = buf ? entry : -1;
+    c->rdump.it = buf ? it : -1;
+    c->rdump.refine = after_refine ? 1 : 0;
     return LAFSE3_OK;
 }
 

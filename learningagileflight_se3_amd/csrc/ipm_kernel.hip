@@ -45,6 +45,17 @@ constexpr int TRACE_W = 16;
 constexpr int DUMP_STEP_W = (MAXN + 1) * NX + MAXN * NU + MAXN * NX;
 constexpr int DUMP_W = 2 * DUMP_STEP_W + 2 * MAXN * NU + 2 * (MAXN + 1) * 3;
 static_assert(DUMP_W == 3732, "lafse3.h documents the dump record as 3732 doubles per instance");
+// restoration dump record (lafse3_debug_dump_resto): the step [dx | du | lam+ | dp | dn], the iterate [x | u | lam |
+// zLu | zUu | zLw | zUw | p | n | z_p | z_n], the reference point [x_R | u_R], RD_NSCAL scalars, then the record of the
+// entry's least-squares multiplier solve [lam+ | ok | IPM iterations before the entry]
+constexpr int RD_STEP_W = DUMP_STEP_W + 2 * MAXN * NX;
+constexpr int RD_POINT_W = DUMP_W - DUMP_STEP_W + 4 * MAXN * NX;
+constexpr int RD_REF_W = (MAXN + 1) * NX + MAXN * NU;
+constexpr int RD_NSCAL = 6;
+constexpr int RD_SCAL = RD_STEP_W + RD_POINT_W + RD_REF_W;
+constexpr int RD_LSQ = RD_SCAL + RD_NSCAL;
+constexpr int RD_W = RD_LSQ + MAXN * NX + 2;
+static_assert(RD_W == 9153, "lafse3.h documents the restoration dump record as 9153 doubles per instance");
 
 enum Mode : int { MODE_SOLVE = 0, MODE_OBJECTIVE = 1, MODE_GRAD = 2, MODE_GETINPUT = 3, MODE_REWARD = 4 };
 enum { ST_SOLVED = 0, ST_ACCEPTABLE = 1, ST_MAXITER = 2, ST_LS_FAIL = 3, ST_NONFINITE = 4, ST_TINY = 5,
@@ -167,6 +178,12 @@ struct KernelArgs {
 struct SensArgs {
     double *dx_out, *du_out;        // B x 7 x (N+1) x 13, B x 7 x N x 4 (each nullable)
     int32_t *sens_out;              // B: 0 ok, 1 the solve did not converge, 2 wrong inertia at z* (nullable)
+};
+// second argument of ipm_kernel_dump: the restoration dump (lafse3_debug_dump_resto).  Not part of KernelArgs, as SensArgs.
+struct RestoDumpArgs {
+    double *buf;                    // RD_W doubles per instance (nullable)
+    int entry, it;                  // the it-th iteration of the entry-th entry into the phase of each solve, 0-based
+    int refine;                     // 0: the step before iterative refinement, 1: after
 };
 // second argument of ipm_kernel_sens_ex (sens_ex.inc): P = the columns of the selected groups
 struct SensExArgs {
@@ -1855,7 +1872,8 @@ template <bool SENS, bool DUMP = false, bool SENSX = false, bool SENSW = false>
 __device__ __attribute__((always_inline)) inline int run_instance(const KernelArgs &A, Smem &S, const int64_t inst,
                                                                  gdouble *ws, const SensArgs *Z = nullptr,
                                                                  const SensExArgs *ZX = nullptr,
-                                                                 const SensWArgs *ZW = nullptr)
+                                                                 const SensWArgs *ZW = nullptr,
+                                                                 const RestoDumpArgs *ZR = nullptr)
 {
     const int lane = lane_id();
     const lafse3_params &prm = A.prm;
@@ -2437,8 +2455,15 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
     // the start point enters the filter and the restoration phase runs (oracle orc_ipm); its iterations count as
     // iterations (the failed one not: `it` was not advanced past it)
     nfilt = filter_add(FT, FP, nfilt, r_th0, r_ph0);
-    const RestoOut ro = restoration(prm, M, at, S, C, ws, (gdouble *)(A.rws + slot_id() * (int64_t)RWS_SIZE), mu,
-                                    r_th0, r_ph0, nfilt, prm.max_iter - it);
+    RestoOut ro;
+    if constexpr (DUMP) {   // the restoration dump of this entry, when it is the armed one
+        double *rrec = (ZR->buf && resto_entries == ZR->entry) ? ZR->buf + inst * (int64_t)RD_W : nullptr;
+        ro = restoration<true>(prm, M, at, S, C, ws, (gdouble *)(A.rws + slot_id() * (int64_t)RWS_SIZE), mu, r_th0,
+                               r_ph0, nfilt, prm.max_iter - it, rrec, ZR->it, ZR->refine);
+    } else {
+        ro = restoration<false>(prm, M, at, S, C, ws, (gdouble *)(A.rws + slot_id() * (int64_t)RWS_SIZE), mu, r_th0, r_ph0,
+                                nfilt, prm.max_iter - it);
+    }
     resto_entries++;
     iters += ro.iters;
     sweeps += ro.sweeps;
@@ -2737,10 +2762,10 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_sens(KernelArgs A, SensArgs 
     }
 }
 
-// The persistent solver whose debug dump carries the iterate (lafse3_debug_dump armed, lafse3_ocp_solve launches): as
-// ipm_kernel_sens a further instantiation of run_instance in a kernel of its own with the plain queue-head loop, so
-// that ipm_kernel's code is what it is without the extra stores.
-__global__ __launch_bounds__(64, 1) void ipm_kernel_dump(KernelArgs A)
+// The persistent solver whose debug dump carries the iterate (lafse3_debug_dump or lafse3_debug_dump_resto armed,
+// lafse3_ocp_solve launches): as ipm_kernel_sens a further instantiation of run_instance in a kernel of its own with the
+// plain queue-head loop, so that ipm_kernel's code is what it is without the extra stores.
+__global__ __launch_bounds__(64, 1) void ipm_kernel_dump(KernelArgs A, RestoDumpArgs Z)
 {
     Smem &S = instance_smem();
     gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
@@ -2752,7 +2777,7 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_dump(KernelArgs A)
         typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
         KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         __asm__ volatile("" : "+s"(Ap));
-        run_instance<false, true>(*(const KernelArgs *)Ap, S, inst, ws);
+        run_instance<false, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, nullptr, nullptr, &Z);
     }
 }
 

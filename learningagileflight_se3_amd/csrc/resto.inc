@@ -642,16 +642,59 @@ __device__ __noinline__ double resto_residual(const Model &M, const Attitude &at
     return nres / (fmin(nsol, 1e6 * nrhs) + nrhs);
 }
 
-// Newton step with IPOPT's iterative refinement (oracle newton_step_resto); 0 on wrong inertia
+// Restoration dump record (lafse3_debug_dump_resto, RD_* in ipm_kernel.hip), written by ipm_kernel_dump only.  The
+// step: dx | du | lam+ | dp | dn, stage-major and padded to MAXN
+__device__ __noinline__ void resto_dump_step(const Smem &S, const gdouble *rs, int N, double *out)
+{
+    const int lane = lane_id();
+    for (int e = lane; e < (N + 1) * NX; e += WAVE) out[e] = S.dx[(e % NX) * SX + e / NX];
+    out += (MAXN + 1) * NX;
+    for (int e = lane; e < N * NU; e += WAVE) out[e] = S.du[(e % NU) * SX + e / NU];
+    out += MAXN * NU;
+    for (int e = lane; e < N * NX; e += WAVE) {
+        const int idx = (e % NX) * SX + e / NX;
+        out[e] = S.lamp[idx];
+        out[MAXN * NX + e] = rs[R_DP + idx];
+        out[2 * MAXN * NX + e] = rs[R_DN + idx];
+    }
+}
+// the iterate the dumped system is formed at (dump_point's arrays, then p | n | z_p | z_n) and the reference point
+// x_R | u_R
+__device__ __noinline__ void resto_dump_point(const Smem &S, const gdouble *ws, const gdouble *rs, int N, double *out)
+{
+    const int lane = lane_id();
+    dump_point(S, ws, N, out);
+    out += DUMP_W - DUMP_STEP_W;
+    for (int e = lane; e < N * NX; e += WAVE) {
+        const int idx = (e % NX) * SX + e / NX;
+        out[e] = rs[R_P + idx];
+        out[MAXN * NX + e] = rs[R_N + idx];
+        out[2 * MAXN * NX + e] = rs[R_ZP + idx];
+        out[3 * MAXN * NX + e] = rs[R_ZN + idx];
+    }
+    out += 4 * MAXN * NX;
+    for (int e = lane; e < (N + 1) * NX; e += WAVE) out[e] = rs[R_XR + (e % NX) * SX + e / NX];
+    out += (MAXN + 1) * NX;
+    for (int e = lane; e < N * NU; e += WAVE) out[e] = rs[R_UR + (e % NU) * SX + e / NU];
+}
+
+// Newton step with IPOPT's iterative refinement (oracle newton_step_resto); 0 on wrong inertia.  DUMP: rec (nullable)
+// is the dump record of this iteration, its step the refined one when drefine; the production kernels instantiate
+// DUMP = false, which compiles none of it.
+template <bool DUMP>
 __device__ __noinline__ int resto_newton(const Model &M, const Attitude &at, Smem &S, const Ctl &C, gdouble *ws, gdouble *rs,
-                                         double mu, double eta, double dw, int &sweeps)
+                                         double mu, double eta, double dw, int &sweeps, [[maybe_unused]] double *rec = nullptr,
+                                         [[maybe_unused]] int drefine = 0)
 {
     WS_TRAJ(ws);
     const int lane = lane_id();
     const int ok = resto_riccati(M, at, S, C, ws, rs, mu, eta, dw, 0, 0);
     sweeps++;
     if (!ok) return 0;
+    if constexpr (DUMP)
+        if (rec && !drefine) resto_dump_step(S, rs, C.N, rec);
     double ratio = resto_residual(M, at, S, C, ws, rs, mu, eta, dw);
+    [[maybe_unused]] const double ratio_pre = ratio;
     gdouble *bdx = ws + WS_BDX, *bdu = ws + WS_BDU, *blp = ws + WS_BLP, *bdp = rs + R_BP, *bdn = rs + R_BN;
     for (int step = 0; step < 10; ++step) {
         if (step >= 1 && ratio <= 1e-10) break;
@@ -686,6 +729,15 @@ __device__ __noinline__ int resto_newton(const Model &M, const Attitude &at, Sme
             break;
         }
         ratio = nr;
+    }
+    if constexpr (DUMP) {
+        if (rec) {
+            if (drefine) resto_dump_step(S, rs, C.N, rec);
+            if (lane == 0) {
+                double *sc = rec + RD_SCAL;
+                sc[0] = mu; sc[1] = eta; sc[2] = dw; sc[3] = 1.0; sc[4] = ratio_pre; sc[5] = ratio;
+            }
+        }
     }
     return 1;
 }
@@ -943,9 +995,14 @@ struct RestoOut {
 // (th_ref, ph_ref) the start point, which the caller has added to the original filter (nfilt entries).  status 0:
 // an iterate acceptable to the original problem was found (multipliers reset as IPOPT does); otherwise the final
 // status (ST_RESTO_FAIL, ST_INFEASIBLE, ST_MAXITER, ST_REG_FAIL, ST_NONFINITE) with the wave back at the start point.
+// DUMP: rdump (nullable) is this instance's restoration dump record when this entry is the armed one; iteration dit of
+// the entry is dumped (lafse3_debug_dump_resto); the production kernels instantiate DUMP = false, which compiles none
+// of it.
+template <bool DUMP>
 __device__ __noinline__ RestoOut restoration(const lafse3_params &prm, const Model &M, const Attitude &at, Smem &S,
                                              const Ctl &C, gdouble *ws, gdouble *rs, double mu_o, double th_ref, double ph_ref,
-                                             int onfilt, int iters_left)
+                                             int onfilt, int iters_left, [[maybe_unused]] double *rdump = nullptr,
+                                             [[maybe_unused]] int dit = 0, [[maybe_unused]] int drefine = 0)
 {
     WS_TRAJ(ws);
     const int lane = lane_id();
@@ -1020,6 +1077,11 @@ __device__ __noinline__ RestoOut restoration(const lafse3_params &prm, const Mod
     vm_sync();
     // constraint multipliers: least-squares estimate (constr_mult_init_max = 1000)
     if (resto_riccati(M, at, S, C, ws, rs, mu0, sqrt(mu0), 0.0, 1, 0)) {
+        if constexpr (DUMP)   // the least-squares multipliers before the cut
+            if (rdump) {
+                for (int e = lane; e < N * NX; e += WAVE) rdump[RD_LSQ + e] = LP[(e % NX) * SX + e / NX];
+                if (lane == 0) rdump[RD_LSQ + MAXN * NX] = 1.0;
+            }
         double mx = 0.0;
         if (lane < N)
 #pragma unroll
@@ -1029,7 +1091,12 @@ __device__ __noinline__ RestoOut restoration(const lafse3_params &prm, const Mod
 #pragma unroll
             for (int i = 0; i < NX; ++i) LAM[i * SX + lane] = LP[i * SX + lane];
         vm_sync();
+    } else {
+        if constexpr (DUMP)
+            if (rdump && lane == 0) rdump[RD_LSQ + MAXN * NX] = 0.0;
     }
+    if constexpr (DUMP)   // the IPM iterations taken before this entry
+        if (rdump && lane == 0) rdump[RD_LSQ + MAXN * NX + 1] = prm.max_iter - iters_left;
     out.sweeps++;
     double mu = mu0, eta = sqrt(mu0), tau = fmax(0.99, 1.0 - mu0);
     int nfilt = 0;
@@ -1061,11 +1128,20 @@ __device__ __noinline__ RestoOut restoration(const lafse3_params &prm, const Mod
             }
         }
         // direction with inertia correction
-        int ok = resto_newton(M, at, S, C, ws, rs, mu, eta, 0.0, out.sweeps);
+        [[maybe_unused]] double *rec = nullptr;
+        if constexpr (DUMP) {
+            if (rdump && out.iters == dit) {
+                rec = rdump;
+                resto_dump_point(S, ws, rs, N, rec + RD_STEP_W);
+            }
+        }
+        // (a lambda around the two calls would hide the wave-constant addresses of M, at, S and C from the
+        // interprocedural constant propagation, which folds them into resto_newton and its callees)
+        int ok = resto_newton<DUMP>(M, at, S, C, ws, rs, mu, eta, 0.0, out.sweeps, rec, drefine);
         if (!ok) {
             double dw = (dw_last == 0.0) ? 1e-4 : fmax(1e-20, dw_last / 3.0);
             for (;;) {
-                ok = resto_newton(M, at, S, C, ws, rs, mu, eta, dw, out.sweeps);
+                ok = resto_newton<DUMP>(M, at, S, C, ws, rs, mu, eta, dw, out.sweeps, rec, drefine);
                 if (ok) { dw_last = dw; break; }
                 dw *= (dw_last == 0.0) ? 100.0 : 8.0;
                 if (dw > 1e40) break;

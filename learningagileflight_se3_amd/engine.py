@@ -200,6 +200,19 @@ class Engine:
         self._dump_buf = buf
         check(self._L.lafse3_debug_dump(self._ctx, _ptr(buf), int(it), int(after_refine)), "lafse3_debug_dump")
 
+    def debug_dump_resto(self, buf=None, entry: int = 0, it: int = 0, after_refine: bool = False):
+        """Debug: the restoration phase's Newton step of iteration `it` of the entry-th entry into the phase (both
+        0-based) of each solve, with the iterate and reference point it was formed at, its scalars and the entry's
+        least-squares multiplier record, into a (instances, 9153) float64 device tensor (lafse3_debug_dump_resto in
+        lafse3.h; ocp_solve launches only).  None disables."""
+        if buf is not None and (buf.dtype != torch.float64 or not buf.is_contiguous() or buf.device != self.device
+                                or buf.shape[-1] != 9153):
+            raise ValueError("debug_dump_resto: a contiguous (instances, 9153) float64 tensor on the engine's device "
+                             "is required")
+        self._rdump_buf = buf
+        check(self._L.lafse3_debug_dump_resto(self._ctx, _ptr(buf), int(entry), int(it), int(after_refine)),
+              "lafse3_debug_dump_resto")
+
     def debug_timers(self, buf=None):
         """Debug: per-instance phase timers + placement record into an (instances, 32) int64 device tensor (None disables)."""
         self._timer_buf = buf

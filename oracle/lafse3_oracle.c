@@ -51,6 +51,16 @@
  * [x | u | lam | zLu | zUu | zLw | zUw], each padded to NMAX_DUMP stages */
 #define DUMP_STEP_W ((NMAX_DUMP + 1) * NX + NMAX_DUMP * NU + NMAX_DUMP * NX)
 #define DUMP_W (2 * DUMP_STEP_W + 2 * NMAX_DUMP * NU + 2 * (NMAX_DUMP + 1) * 3)
+/* per-instance record of orc_debug_dump_resto (the record of lafse3_debug_dump_resto, include/lafse3.h):
+ * the step [dx | du | lam+ | dp | dn], the iterate [x | u | lam | zLu | zUu | zLw | zUw | p | n | z_p | z_n], the
+ * reference point [x_R | u_R], RD_NSCAL scalars, then the least-squares record [lam+ | ok | iterations before] */
+#define RD_STEP_W (DUMP_STEP_W + 2 * NMAX_DUMP * NX)
+#define RD_POINT_W (DUMP_W - DUMP_STEP_W + 4 * NMAX_DUMP * NX)
+#define RD_REF_W ((NMAX_DUMP + 1) * NX + NMAX_DUMP * NU)
+#define RD_NSCAL 6
+#define RD_SCAL (RD_STEP_W + RD_POINT_W + RD_REF_W)
+#define RD_LSQ (RD_SCAL + RD_NSCAL)
+#define RD_W (RD_LSQ + NMAX_DUMP * NX + 2)
 
 typedef struct {
     /* model (quad_policy.py:37, quad_model.py:37) */
@@ -446,6 +456,8 @@ typedef struct {
     int trace_iters;
     double *dump;      /* debug: Newton step of iteration dump_it */
     int dump_it, dump_refine;
+    double *rdump;     /* debug: restoration Newton step of iteration rdump_it of entry rdump_entry (RD_W) */
+    int rdump_entry, rdump_it, rdump_refine;
     /* optimality error at the last iterate (IPOPT's "Overall NLP error" and its unscaled parts) */
     double fin_err, fin_dual, fin_primal, fin_compl;
 } orc_ws;
@@ -1742,8 +1754,54 @@ static double kkt_residual_resto(const orc_params *P, orc_ws *W, resto_t *R, dou
     return nres / (fmin(nsol, 1e6 * nrhs) + nrhs);
 }
 
-/* Newton step with IPOPT's iterative refinement (refine_loop's rule) on the restoration system */
-static int newton_step_resto(const orc_params *P, orc_ws *W, resto_t *R, double delta_w)
+static void dump_step_resto(const orc_ws *W, const resto_t *R, double *out)
+{
+    const int N = W->N;
+    memcpy(out, W->dx, sizeof(double) * (N + 1) * NX);
+    out += (NMAX_DUMP + 1) * NX;
+    memcpy(out, W->du, sizeof(double) * N * NU);
+    out += NMAX_DUMP * NU;
+    memcpy(out, W->lamp, sizeof(double) * N * NX);
+    out += NMAX_DUMP * NX;
+    memcpy(out, R->dp, sizeof(double) * N * NX);
+    out += NMAX_DUMP * NX;
+    memcpy(out, R->dn, sizeof(double) * N * NX);
+}
+
+/* the iterate and the reference point of the dumped restoration system (behind the step arrays) */
+static void dump_point_resto(const orc_ws *W, const resto_t *R, double *pt)
+{
+    const int N = W->N;
+    memcpy(pt, W->x, sizeof(double) * (N + 1) * NX);
+    pt += (NMAX_DUMP + 1) * NX;
+    memcpy(pt, W->u, sizeof(double) * N * NU);
+    pt += NMAX_DUMP * NU;
+    memcpy(pt, W->lam, sizeof(double) * N * NX);
+    pt += NMAX_DUMP * NX;
+    memcpy(pt, W->zLu, sizeof(double) * N * NU);
+    pt += NMAX_DUMP * NU;
+    memcpy(pt, W->zUu, sizeof(double) * N * NU);
+    pt += NMAX_DUMP * NU;
+    memcpy(pt, W->zLw, sizeof(double) * (N + 1) * 3);
+    pt += (NMAX_DUMP + 1) * 3;
+    memcpy(pt, W->zUw, sizeof(double) * (N + 1) * 3);
+    pt += (NMAX_DUMP + 1) * 3;
+    memcpy(pt, R->p, sizeof(double) * N * NX);
+    pt += NMAX_DUMP * NX;
+    memcpy(pt, R->n, sizeof(double) * N * NX);
+    pt += NMAX_DUMP * NX;
+    memcpy(pt, R->zp, sizeof(double) * N * NX);
+    pt += NMAX_DUMP * NX;
+    memcpy(pt, R->zn, sizeof(double) * N * NX);
+    pt += NMAX_DUMP * NX;
+    memcpy(pt, R->xR, sizeof(double) * (N + 1) * NX);
+    pt += (NMAX_DUMP + 1) * NX;
+    memcpy(pt, R->uR, sizeof(double) * N * NU);
+}
+
+/* Newton step with IPOPT's iterative refinement (refine_loop's rule) on the restoration system; rec (nullable): the
+ * dump record of this iteration, refined step when dump_refine */
+static int newton_step_resto(const orc_params *P, orc_ws *W, resto_t *R, double delta_w, double *rec, int dump_refine)
 {
     const int N = W->N;
     W->refine = 0;
@@ -1751,7 +1809,9 @@ static int newton_step_resto(const orc_params *P, orc_ws *W, resto_t *R, double 
     int rc = riccati_resto(P, W, R, delta_w, 0);
     W->sweeps++;
     if (rc != 0) return rc;
+    if (rec && !dump_refine) dump_step_resto(W, R, rec);
     double ratio = kkt_residual_resto(P, W, R, delta_w);
+    const double ratio_pre = ratio;
     double dx[(NMAX + 1) * NX], du[NMAX * NU], dl[NMAX * NX], dp[NMAX * NX], dn[NMAX * NX];
     for (int step = 0; step < 10; ++step) {
         if (step >= 1 && ratio <= 1e-10) break;
@@ -1783,6 +1843,11 @@ static int newton_step_resto(const orc_params *P, orc_ws *W, resto_t *R, double 
             break;
         }
         ratio = nr;
+    }
+    if (rec) {
+        if (dump_refine) dump_step_resto(W, R, rec);
+        double *sc = rec + RD_SCAL;
+        sc[0] = R->mu; sc[1] = R->eta; sc[2] = delta_w; sc[3] = 1.0; sc[4] = ratio_pre; sc[5] = ratio;
     }
     return 0;
 }
@@ -2053,12 +2118,20 @@ static int orc_restoration(const orc_params *P, const orc_inst *I, orc_ws *W, do
     memset(W->lam, 0, sizeof(double) * N * NX);
     W->refine = 0;
     R->refine = 0;
-    if (riccati_resto(P, W, R, 0.0, 1) == 0) {
+    double *const rdump = (W->rdump && W->restos == W->rdump_entry) ? W->rdump : NULL;
+    const int lsq_ok = riccati_resto(P, W, R, 0.0, 1) == 0;
+    if (lsq_ok) {
         double mx = 0;
         for (int e = 0; e < N * NX; ++e) mx = fmax(mx, fabs(W->lamp[e]));
         if (mx <= 1e3) memcpy(W->lam, W->lamp, sizeof(double) * N * NX);
     }
+    if (rdump) {   /* the least-squares multipliers before the cut, and the IPM iterations taken before this entry */
+        if (lsq_ok) memcpy(rdump + RD_LSQ, W->lamp, sizeof(double) * N * NX);
+        rdump[RD_LSQ + NMAX_DUMP * NX] = lsq_ok;
+        rdump[RD_LSQ + NMAX_DUMP * NX + 1] = P->max_iter - *iters_left;
+    }
     W->sweeps++;
+    int rit = 0;   /* iterations of this entry */
     double tau = fmax(0.99, 1.0 - mu);
     double filt_t[FILTER_MAX], filt_p[FILTER_MAX];
     int nfilt = 0;
@@ -2100,11 +2173,13 @@ static int orc_restoration(const orc_params *P, const orc_inst *I, orc_ws *W, do
         }
         /* direction with inertia correction */
         double dw = 0.0;
-        int rc = newton_step_resto(P, W, R, 0.0);
+        double *const rec = (rdump && rit == W->rdump_it) ? rdump : NULL;
+        if (rec) dump_point_resto(W, R, rec + RD_STEP_W);
+        int rc = newton_step_resto(P, W, R, 0.0, rec, W->rdump_refine);
         if (rc != 0) {
             dw = (dw_last == 0.0) ? 1e-4 : fmax(1e-20, dw_last / 3.0);
             for (;;) {
-                rc = newton_step_resto(P, W, R, dw);
+                rc = newton_step_resto(P, W, R, dw, rec, W->rdump_refine);
                 if (rc == 0) { dw_last = dw; break; }
                 dw *= (dw_last == 0.0) ? 100.0 : 8.0;
                 if (dw > 1e40) break;
@@ -2148,6 +2223,7 @@ static int orc_restoration(const orc_params *P, const orc_inst *I, orc_ws *W, do
         }
         take_step_resto(W, R, alpha, az, mu);
         W->iters++;
+        rit++;
         (*iters_left)--;
 #ifdef ORC_RTRACE
         fprintf(stderr, "  resto %4d mu %.2e E0 %.3e [d %.2e p %.2e c %.2e] thR %.3e phR %.6e gBD %.2e amax %.2e az %.2e "
@@ -2888,6 +2964,15 @@ static double *g_dump = NULL;
 static int g_dump_it = -1, g_dump_refine = 0;
 void orc_debug_trace(double *buf, int iters) { g_trace = buf; g_trace_iters = iters; }
 void orc_debug_dump(double *buf, int it, int after_refine) { g_dump = buf; g_dump_it = it; g_dump_refine = after_refine; }
+static double *g_rdump = NULL;
+static int g_rdump_entry = -1, g_rdump_it = -1, g_rdump_refine = 0;
+/* restoration Newton step of iteration `it` of the entry-th entry into the phase (both 0-based) of each solve of
+ * subsequent orc_solve_q calls into buf (B x RD_W): the record of lafse3_debug_dump_resto (include/lafse3.h) */
+void orc_debug_dump_resto(double *buf, int entry, int it, int after_refine)
+{
+    g_rdump = buf; g_rdump_entry = entry; g_rdump_it = it; g_rdump_refine = after_refine;
+}
+int orc_debug_dump_resto_width(void) { return RD_W; }
 /* Debug: per instance 4 doubles [overall NLP error (scaled, IPOPT's convergence measure), unscaled dual
  * infeasibility, primal infeasibility, unscaled complementarity] at the last iterate of later solves */
 static double *g_final_err = NULL;
@@ -2908,6 +2993,10 @@ int orc_solve_q(const orc_params *P, int64_t B, const double *ini, const double 
         W->dump = g_dump ? g_dump + b * (int64_t)DUMP_W : NULL;
         W->dump_it = g_dump_it;
         W->dump_refine = g_dump_refine;
+        W->rdump = g_rdump ? g_rdump + b * (int64_t)RD_W : NULL;
+        W->rdump_entry = g_rdump_entry;
+        W->rdump_it = g_rdump_it;
+        W->rdump_refine = g_rdump_refine;
         orc_inst I;
         make_inst(ini + b * NX, goal + b * 3, ptra + b * 3, qtra + b * 4, t[b], ulast ? ulast + b * 4 : NULL, &I);
         int st = orc_ipm(P, &I, W);
@@ -3212,6 +3301,7 @@ int orc_sol_gradient(const orc_params *P, int64_t B, const double *ini, const do
         W->dump = NULL;
         W->dump_it = -1;
         W->dump_refine = 0;
+        W->rdump = NULL;
         orc_inst I;
         make_inst(ini + b * NX, goal + b * 3, p, q, t, ul, &I);
         if (P->grad_mode == 1 && j >= 1 && j <= 6) {   /* IFT: these probes come from the nominal job */

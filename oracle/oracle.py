@@ -96,6 +96,8 @@ def _bind(L):
         L.orc_num_threads.restype = ctypes.c_int
         L.orc_debug_trace.argtypes = [pd, ctypes.c_int]
         L.orc_debug_dump.argtypes = [pd, ctypes.c_int, ctypes.c_int]
+        L.orc_debug_dump_resto.argtypes = [pd, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.orc_debug_dump_resto_width.restype = ctypes.c_int
         L.orc_debug_final_err.argtypes = [pd]
         L.orc_debug_grad_iters.argtypes = [pi]
         L.orc_set_num_threads.argtypes = [ctypes.c_int]
@@ -284,6 +286,17 @@ def debug_dump(buf=None, it=-1, after_refine=False):
     global _dump_keep
     _dump_keep = buf
     lib().orc_debug_dump(_ptr(buf), int(it), int(after_refine))
+
+
+def debug_dump_resto(buf=None, entry=-1, it=-1, after_refine=False):
+    """Debug: the restoration phase's Newton step of iteration `it` of the entry-th entry into the phase (both
+    0-based) of each solve, the iterate and reference point it was formed at, its scalars and the least-squares
+    multiplier record of that entry into buf (B, 9153): the record of lafse3_debug_dump_resto (lafse3.h)."""
+    global _rdump_keep
+    if buf is not None:
+        assert buf.dtype == np.float64 and buf.flags.c_contiguous and buf.shape[-1] == lib().orc_debug_dump_resto_width()
+    _rdump_keep = buf
+    lib().orc_debug_dump_resto(_ptr(buf), int(entry), int(it), int(after_refine))
 
 
 def debug_final_err(buf=None, fast: bool = False):

@@ -26,7 +26,7 @@ def lib():
 
 def test_header_symbols_exported(lib):
     names = _declared()
-    assert len(names) >= 15
+    assert len(names) >= 15 and "lafse3_debug_dump" in names and "lafse3_debug_dump_resto" in names
     for n in names:
         assert hasattr(lib, n), f"{n} declared in lafse3.h but not exported"
         assert n in _lib.SIGNATURES, f"{n} has no ctypes signature in _lib.SIGNATURES"
