@@ -541,6 +541,8 @@ __device__ __attribute__((always_inline)) inline double kkt_residual(const Model
     const gdouble *cs = ws + WS_CS;
     double nres = 0, nsol = 0, nrhs = 0;
     const int k = lane;
+    // soc reaches linear_solve in a vector register; as a scalar, the defect loads below sit behind one branch
+    const int usoc = uni(soc);
     // ---- u rows (quad_OC.py NLP gradient w.r.t. U_k: thrust + smoothing of stages k and k+1)
     if (k < N) {
         double xk[NX], lpk[NX], duk[NU], dun[NU], dupr[NU], zl[NU], zu[NU], dq[4], lq[3];
@@ -603,7 +605,11 @@ __device__ __attribute__((always_inline)) inline double kkt_residual(const Model
         for (int i = 0; i < NX; ++i) {
             dxk[i] = DX[i * SX + k];
             dx1[i] = DX[i * SX + k + 1];
-            cv[i] = soc ? (double)cs[i * SX + k] : 0.0;
+            cv[i] = 0.0;
+        }
+        if (usoc) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) cv[i] = cs[i * SX + k];
         }
 #pragma unroll
         for (int a = 0; a < NU; ++a) duk[a] = DU[a * SX + k];
@@ -614,7 +620,7 @@ __device__ __attribute__((always_inline)) inline double kkt_residual(const Model
         double ro[NX];
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
-            double c = soc ? cv[i] : xn[i] - S.x[i * SX + k + 1];
+            double c = usoc ? cv[i] : xn[i] - S.x[i * SX + k + 1];
             double acc = c - dx1[i] + ax[i] + bd[i];
             ro[i] = acc;
             nres = fmax(nres, fabs(acc));
@@ -626,19 +632,24 @@ __device__ __attribute__((always_inline)) inline double kkt_residual(const Model
 #pragma unroll
         for (int i = 0; i < NX; ++i) rc[i * SX + k] = ro[i];
     }
-    // ---- x rows of stages 1..N-1 (lanes 1..N-1) and the terminal rows (lane N)
-    if (k >= 1 && k < N) {
+    // ---- x rows of stages 1..N-1 (lanes 1..N-1) and the terminal rows (lane N) in one instruction stream: the loads,
+    // the cost gradient (weight 0 at stage N) and the barrier terms are the same code for both.  Lane N has no u,
+    // lambda or lambda+ of its own: it reads stage N-1's (clamped index) and drops what it forms from them, the stage
+    // Hessian and A^T lambda+; its own diagonal, the wqf block and g - lambda+_{N-1} + o are chosen per lane below.
+    if (k >= 1 && k <= N) {
+        const bool term = (k == N);
+        const int ku = min(k, N - 1);
         double xk[NX], uk[NU], lk[NX], dxk[NX], lpk[NX], lpm[NX], zl[3], zu[3];
         load_stage(S, k, xk);
-        load_u(S, k, uk);
+        load_u(S, ku, uk);
         double sdu = 0.0;
 #pragma unroll
-        for (int a = 0; a < NU; ++a) sdu += DU[a * SX + k];
+        for (int a = 0; a < NU; ++a) sdu += DU[a * SX + ku];
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
-            lk[i] = LAM[i * SX + k];
+            lk[i] = LAM[i * SX + ku];
             dxk[i] = DX[i * SX + k];
-            lpk[i] = LP[i * SX + k];
+            lpk[i] = LP[i * SX + ku];
             lpm[i] = LP[i * SX + k - 1];
         }
 #pragma unroll
@@ -647,83 +658,67 @@ __device__ __attribute__((always_inline)) inline double kkt_residual(const Model
             zu[c] = ZUW[c * SX + k];
         }
         double o[NX];
-        {
-            StageHess H;
-            stage_hessian(M, at, s, S.wk[k], xk, uk, lk, H);
-            Hxx_times(H, dxk, o);
+        StageHess H;
+        stage_hessian(M, at, s, S.wk[ku], xk, uk, lk, H);
+        Hxx_times(H, dxk, o);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) o[6 + i] += H.qu[i] * sdu;
-        }
+        for (int i = 0; i < 4; ++i) o[6 + i] += H.qu[i] * sdu;
         double atl[NX], g[NX];
         At_times(M, xk, uk, lpk, atl);
-        grad_x(M, at, S, C, k, xk, g);
+        state_cost_grad(M, at, S.goal, S.ptra, term ? 0.0 : S.wk[ku], xk, g);   // unscaled: s enters below
+        double gb[3], sg[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            double gb, sg;
-            bar_terms(xk[10 + c], C.wlo, C.whi, zl[c], zu[c], C.mu, gb, sg);
-            g[10 + c] += gb;
-            o[10 + c] += sg * dxk[10 + c];
+            bar_terms(xk[10 + c], C.wlo, C.whi, zl[c], zu[c], C.mu, gb[c], sg[c]);
+            o[10 + c] += sg[c] * dxk[10 + c];
         }
-        double ro[NX];
+        // the terminal rows' quaternion block: dw dx, and the goal-attitude Hessian where it is weighted
+        double oq[4];
 #pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            double acc = g[i] - lpm[i] + o[i] + dw * dxk[i] + atl[i];
-            ro[i] = acc;
-            nres = fmax(nres, fabs(acc));
-            nrhs = fmax(nrhs, fabs(g[i]));
-            nsol = fmax(nsol, fabs(dxk[i]));
+        for (int i = 6; i < 10; ++i) {
+            double a = dw * dxk[i];
+            if (M.wqf != 0.0)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a += s * M.wqf * (-2 * S.at.Sg[(i - 6) * 4 + j]) * dxk[6 + j];
+            oq[i - 6] = a;
+        }
+        // The rows, every rounding written out as the two separate branches compiled before they were folded (a fused
+        // multiply-add where the compiler had contracted, separate operations where it had not):
+        //   stage     (((s g - lam+_{k-1}) + o) + dw dx) + A^T lam+, with o's single products of rows 0..5 fused
+        //   terminal  (s g - lam+_{N-1}) + o_N, with o_N = coefficient * dx fused (rows 0..5 and 10..12) and the sum
+        //             above for rows 6..9
+        double ro[NX];
+        {
+#pragma clang fp contract(off)
+            const double s2 = s * 2;
+            const double cr = term ? fma(s2, M.wrf, dw) : H.hr, cvel = term ? fma(s2, M.wvf, dw) : H.hv;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+                double gi, t, a;
+                if (i < 10) {
+                    gi = s * g[i];
+                    t = fma(s, g[i], -lpm[i]);
+                } else {
+                    gi = fma(s, g[i], gb[i - 10]);
+                    t = gi - lpm[i];
+                }
+                if (i < 6) {
+                    a = fma(i < 3 ? cr : cvel, dxk[i], t);
+                } else if (i < 10) {
+                    a = t + (term ? oq[i - 6] : o[i]);
+                } else {
+                    const double ct = fma(s2, M.wwf, sg[i - 10]) + dw;
+                    a = term ? fma(ct, dxk[i], t) : t + o[i];
+                }
+                const double acc = term ? a : fma(dw, dxk[i], a) + atl[i];
+                ro[i] = acc;
+                nres = fmax(nres, fabs(acc));
+                nrhs = fmax(nrhs, fabs(gi));
+                nsol = fmax(nsol, fabs(dxk[i]));
+            }
         }
 #pragma unroll
         for (int i = 0; i < NX; ++i) rq[i * SX + k] = ro[i];
-    } else if (k == N) {
-        // terminal x rows
-        double xN[NX], dxN[NX], lpm[NX], zl[3], zu[3], g[NX];
-        load_stage(S, N, xN);
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            dxN[i] = DX[i * SX + N];
-            lpm[i] = LP[i * SX + N - 1];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            zl[c] = ZLW[c * SX + N];
-            zu[c] = ZUW[c * SX + N];
-        }
-        state_cost_grad(M, at, S.goal, S.ptra, 0.0, xN, g);
-#pragma unroll
-        for (int i = 0; i < NX; ++i) g[i] *= s;
-        double o[NX];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            o[i] = (s * 2 * M.wrf + dw) * dxN[i];
-            o[3 + i] = (s * 2 * M.wvf + dw) * dxN[3 + i];
-        }
-#pragma unroll
-        for (int i = 6; i < 10; ++i) {
-            double a = dw * dxN[i];
-            if (M.wqf != 0.0)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) a += s * M.wqf * (-2 * S.at.Sg[(i - 6) * 4 + j]) * dxN[6 + j];
-            o[i] = a;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            double gb, sg;
-            bar_terms(xN[10 + c], C.wlo, C.whi, zl[c], zu[c], C.mu, gb, sg);
-            g[10 + c] += gb;
-            o[10 + c] = (s * 2 * M.wwf + sg + dw) * dxN[10 + c];
-        }
-        double ro[NX];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            double acc = g[i] - lpm[i] + o[i];
-            ro[i] = acc;
-            nres = fmax(nres, fabs(acc));
-            nrhs = fmax(nrhs, fabs(g[i]));
-            nsol = fmax(nsol, fabs(dxN[i]));
-        }
-#pragma unroll
-        for (int i = 0; i < NX; ++i) rq[i * SX + N] = ro[i];
     }
     nres = wmax(nres);
     nsol = wmax(nsol);
@@ -1242,13 +1237,15 @@ __device__ inline int filter_add(gdouble *FT, gdouble *FP, int nfilt, double th0
 
 // IPOPT FilterLSAcceptor::CheckAcceptabilityOfTrialPoint (uniform across lanes): switching condition and
 // Armijo with the original step size alpha_test, sufficient decrease otherwise, then the filter
+// pg = pow(-gBD, 2.3) and pt = pow(th0, 1.1) of the reference point (th0, gBD): the caller forms them once per
+// iteration; they are read only when gBD < 0
 __device__ inline int ls_accept(const gdouble *FT, const gdouble *FP, int nfilt, double alpha_test, double tht, double pht, int okt, double th0,
-                                double ph0, double gBD, double theta_max, double theta_min)
+                                double ph0, double gBD, double pg, double pt, double theta_max, double theta_min)
 {
     const double eps = 2.220446049250313e-16;
     int acc = okt && !(tht > theta_max);
     if (acc) {
-        int ftype = (gBD < 0) && (alpha_test * pow(-gBD, 2.3) > pow(th0, 1.1));
+        int ftype = (gBD < 0) && (alpha_test * pg > pt);
         if (ftype && th0 <= theta_min) {
             acc = (pht - ph0 - 1e-8 * alpha_test * gBD) <= 10.0 * eps * fabs(ph0);
         } else {
@@ -1263,6 +1260,17 @@ __device__ inline int ls_accept(const gdouble *FT, const gdouble *FP, int nfilt,
     }
     if (acc && !filter_ok(FT, FP, nfilt, tht, pht)) return 0;
     return acc;
+}
+// the restoration phase's line search (resto.inc): the powers formed where the test needs them, as before
+__device__ inline int ls_accept(const gdouble *FT, const gdouble *FP, int nfilt, double alpha_test, double tht, double pht, int okt, double th0,
+                                double ph0, double gBD, double theta_max, double theta_min)
+{
+    double pg = 0.0, pt = 0.0;
+    if (okt && !(tht > theta_max) && gBD < 0) {
+        pg = pow(-gBD, 2.3);
+        pt = pow(th0, 1.1);
+    }
+    return ls_accept(FT, FP, nfilt, alpha_test, tht, pht, okt, th0, ph0, gBD, pg, pt, theta_max, theta_min);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2252,9 +2260,19 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
             wd_trial = 0;
             in_wd = 1;
         }
+        // the switching condition's powers pow(-rgBD, 2.3) and pow(rth, 1.1), once per iteration: every acceptance
+        // test, the alpha_min set-up and the filter update read them at the reference point (rth, rgBD).  That is the
+        // current iterate (th0, gBD) except on a watchdog trial, whose branch forms them at the watchdog's stored
+        // point; a stopped watchdog makes that point the current one, so they carry over to the line search
+        const int wd_ref = in_wd && !is_tiny && !in_soft_resto;
+        double pw_g = 0.0, pw_t = 0.0;
+        if (gBD < 0 && !is_tiny && !wd_ref) {
+            pw_g = pow(-gBD, 2.3);
+            pw_t = pow(th0, 1.1);
+        }
         double alpha = amax, alpha_test = amax;
         double tht = 0, pht = 0;
-        int soft_step = 0;   // 1: a soft restoration step, 2: one that also passes the original line-search test
+        int soft_step = 0;  // 1: a soft restoration step, 2: one that also passes the original line-search test
         int wd_step = 0, n_rej = 0;   // a watchdog step taken without the filter; rejected trials of the line search
         // IPOPT TrySoftRestoStep (oracle try_soft_resto): the full step min(amax, az) for every variable, accepted
         // when it reduces the primal-dual system error by 0.9999; the original criterion with alpha_test = 0
@@ -2270,7 +2288,7 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
             pht = mt.phi;
             tJ = mt.J;
             tlb = mt.lb;
-            soft_step = 1 + ls_accept(FT, FP, nfilt, 0.0, tht, pht, mt.ok, th0, ph0, gBD, theta_max, theta_min);
+            soft_step = 1 + ls_accept(FT, FP, nfilt, 0.0, tht, pht, mt.ok, th0, ph0, gBD, pw_g, pw_t, theta_max, theta_min);
             alpha = az = alpha_test = as;
         };
         if (is_tiny) {
@@ -2290,13 +2308,17 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
                 rth = wd_th;
                 rph = wd_ph;
                 rgBD = wd_gBD;
+                if (rgBD < 0) {
+                    pw_g = pow(-rgBD, 2.3);
+                    pw_t = pow(rth, 1.1);
+                }
                 const Merit mt = eval_merit(M, at, S, C, ws, amax, mu);
                 trials++;
                 tht = mt.theta;
                 pht = mt.phi;
                 tJ = mt.J;
                 tlb = mt.lb;
-                if (ls_accept(FT, FP, nfilt, amax, tht, pht, mt.ok, rth, rph, rgBD, theta_max, theta_min)) {
+                if (ls_accept(FT, FP, nfilt, amax, tht, pht, mt.ok, rth, rph, rgBD, pw_g, pw_t, theta_max, theta_min)) {
                     accepted = 1;
                     in_wd = 0;
                 } else if (++wd_trial > 3) {
@@ -2317,7 +2339,8 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
             double amin_base = 1e-5;
             if (gBD < 0) {
                 amin_base = fmin(1e-5, 1e-8 * th0 / (-gBD));
-                if (th0 <= theta_min) amin_base = fmin(amin_base, pow(th0, 1.1) / pow(-gBD, 2.3));
+                // (read by the backtracking loop only: a watchdog trial that was taken never gets there)
+                if (th0 <= theta_min) amin_base = fmin(amin_base, pw_t / pw_g);
             }
             const double alpha_min = 0.05 * amin_base;
             if (skip_first == 1) alpha = 0.5 * amax;
@@ -2335,7 +2358,7 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
                 }
                 PT_LS(2);
                 trials++;
-                const int acc_t = ls_accept(FT, FP, nfilt, alpha, tht, pht, okt, th0, ph0, gBD, theta_max, theta_min);
+                const int acc_t = ls_accept(FT, FP, nfilt, alpha, tht, pht, okt, th0, ph0, gBD, pw_g, pw_t, theta_max, theta_min);
                 PT_LS(3);
                 if (acc_t) {
                     accepted = 1;
@@ -2370,7 +2393,7 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
                             tlb = ms.lb;
                         }
                         trials++;
-                        sacc = ls_accept(FT, FP, nfilt, alpha, tht, pht, oks, th0, ph0, gBD, theta_max, theta_min);
+                        sacc = ls_accept(FT, FP, nfilt, alpha, tht, pht, oks, th0, ph0, gBD, pw_g, pw_t, theta_max, theta_min);
                         if (!sacc) {
                             cnt++;
                             theta_trial = tht;
@@ -2412,7 +2435,7 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
         // filter update of an accepted step (a soft step the original criterion rejected leaves it alone)
         if (accepted && !is_tiny && soft_step != 1 && !wd_step) {
             {
-                int ftype = (rgBD < 0) && (alpha_test * pow(-rgBD, 2.3) > pow(rth, 1.1));
+                int ftype = (rgBD < 0) && (alpha_test * pw_g > pw_t);
                 int armijo = (pht - rph - 1e-8 * alpha_test * rgBD) <= 10.0 * eps * fabs(rph);
                 // add ((1-g_th) th0, ph0 - g_ph th0); drop entries it dominates
                 if (soft_step || !ftype || !armijo) nfilt = filter_add(FT, FP, nfilt, rth, rph);
