@@ -12,6 +12,7 @@
  *   lafse3_ocp_sensitivity  ocSolver + dx, du / d(p_tra, a_tra, t)  (the PDP auxiliary system, quad_OC.py:214-306)
  *   lafse3_ocp_sensitivity_ex  the same with ini_state and goal columns and the feedback gain du_0 / dx_0
  *   lafse3_ocp_sensitivity_w   the same with per-instance cost weights and the columns of the ten weights
+ *   lafse3_ocp_solve_rec / lafse3_ocp_vjp   the solve that saves its optimum, and g^T dz* / dparam from it in one sweep
  *
  * Every array argument is a DEVICE pointer (HBM; e.g. a torch.cuda tensor's data_ptr()), owned by
  * the caller, row-major, contiguous.  B is the batch size.  N is params.horizon (<= LAFSE3_MAX_N).
@@ -206,6 +207,51 @@ int lafse3_ocp_sensitivity_w(lafse3_ctx *ctx, int64_t B, const double *ini_state
                              double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
                              int32_t groups, double *dx, double *du, double *gain, int32_t *sens_status,
                              void *stream);
+
+/* Adjoint backward from a saved optimum: the vector-Jacobian product g^T dz* / dparam of a loss gradient g = (g_x, g_u)
+ * with the sensitivities of lafse3_ocp_sensitivity_w, without forming them.  Two calls:
+ *
+ * lafse3_ocp_solve_rec is lafse3_ocp_sensitivity_w called as a plain solve (weights B x LAFSE3_NW or NULL; the outputs
+ * x .. iters are that call's bit for bit; a solver launch for lafse3_reserve, lafse3_last_kernel_ms, the counters and
+ * lafse3_check_device) that also writes the optimum record rec, B x lafse3_rec_width() doubles (2223, independent of the
+ * horizon; required: NULL is LAFSE3_EINVAL).  The record is the point at which the sensitivity passes factorise, i.e.
+ * after the final clamp to the original bounds, in the solver's internal quantities.  One instance, every array
+ * stage-major and padded to LAFSE3_MAX_N stages as the iterate block of lafse3_debug_dump (entries of stages beyond the
+ * horizon are not written):
+ *      0  x    51 x 13   equal to the x output bit for bit
+ *    663  u    50 x 4    equal to the u output bit for bit
+ *    863  lam  50 x 13   multipliers of the problem whose objective is scaled by s (the lam output is lam / s)
+ *   1513  zLu  50 x 4    bound duals of u, lower
+ *   1713  zUu  50 x 4                      upper
+ *   1913  zLw  51 x 3    bound duals of omega, lower (stage 0, which is fixed, holds 0)
+ *   2066  zUw  51 x 3                          upper
+ *   2219  mu             the final barrier parameter
+ *   2220  s              the objective scaling
+ *   2221  status         the solve's status, as a double
+ *   2222  horizon        params.horizon of the solve, as a double
+ *
+ * lafse3_ocp_vjp: grad B x P, grad[b, q] = sum g_x . dx* / dparam_q + sum g_u . du* / dparam_q over the P columns of
+ * `groups`, which are lafse3_ocp_sensitivity_w's (lafse3_sens_columns_w).  g_x B x (N+1) x 13 and g_u B x N x 4 are the
+ * gradients of the loss with respect to the x and u outputs (each nullable: zero).  The first nine arguments must be
+ * the ones the record was solved with, under the same context parameters; ini_state is read from stage 0 of the
+ * record.  K is symmetric, so one factorisation at the recorded point and one sweep on the right-hand side (g_x of
+ * stages 1..N, g_u) give every column: the sweep's result is contracted with dF / dparam_q as the gain of
+ * lafse3_ocp_sensitivity_ex is, and g_x of stage 0 goes to the ini_state columns directly (dx_0 / dini_state is the
+ * identity).  sens_status B (nullable): 0 ok, 1 the recorded status > 1, 2 wrong inertia at z*, 3 the record's horizon
+ * is not the context's (checked before anything is read by horizon); after 1, 2 and 3 the row of grad is zero.
+ * groups == 0, a bit outside the four groups, NULL rec or NULL grad are LAFSE3_EINVAL before any launch.  It uses the
+ * context's workspace (covered by lafse3_reserve) and runs on the caller's stream.  Like lafse3_reward it is not a
+ * solver launch: the timing, counters and device error word of the most recent solver launch are kept. */
+int lafse3_rec_width(void);
+int lafse3_ocp_solve_rec(lafse3_ctx *ctx, int64_t B, const double *ini_state, const double *goal,
+                         const double *p_tra, const double *a_tra, const double *t, const double *u_last,
+                         const double *weights,
+                         double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
+                         double *rec, void *stream);
+int lafse3_ocp_vjp(lafse3_ctx *ctx, int64_t B, const double *ini_state, const double *goal,
+                   const double *p_tra, const double *a_tra, const double *t, const double *u_last,
+                   const double *weights, const double *rec, const double *g_x, const double *g_u,
+                   int32_t groups, double *grad, int32_t *sens_status, void *stream);
 
 /* fp32 twin of lafse3_ocp_solve: the same arguments as float32 device buffers.  Inputs are
  * widened to fp64 and outputs rounded to fp32 on the device; the NLP itself is solved in fp64 (IPOPT's

@@ -75,6 +75,9 @@ SIGNATURES = {
     "lafse3_sens_columns_w": (ctypes.c_int, [_i32]),
     "lafse3_params_weights": (ctypes.c_int, [_P(Params), _P(_d)]),
     "lafse3_ocp_sensitivity_w": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] + [_vp] * 6 + [_i32] + [_vp] * 4 + [_vp]),
+    "lafse3_rec_width": (ctypes.c_int, []),
+    "lafse3_ocp_solve_rec": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] + [_vp] * 6 + [_vp] + [_vp]),
+    "lafse3_ocp_vjp": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] + [_vp] * 3 + [_i32] + [_vp] * 2 + [_vp]),
     "lafse3_objective": (ctypes.c_int, [_vp, _i64] + [_vp] * 7 + [_vp, _vp, _vp]),
     "lafse3_sol_gradient": (ctypes.c_int, [_vp, _i64] + [_vp] * 5 + [_vp, _vp, _vp, _vp]),
     "lafse3_get_input": (ctypes.c_int, [_vp, _i64] + [_vp] * 4 + [_vp, _vp, _vp, _vp]),

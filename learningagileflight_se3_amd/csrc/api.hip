@@ -333,7 +333,7 @@ __global__ void slots_init_kernel(double *R, int32_t *S, int64_t n)
 
 static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t sched_samples = 0,
                   const lafse3::SensArgs *sens = nullptr, const lafse3::SensExArgs *sensx = nullptr,
-                  const lafse3::SensWArgs *sensw = nullptr)
+                  const lafse3::SensWArgs *sensw = nullptr, const lafse3::RecArgs *rec = nullptr)
 {
     if (A.n_inst == 0) return LAFSE3_OK;
     // trajectory scoring (MODE_REWARD) counts nothing and has its own queue head: it leaves the last solver
@@ -392,6 +392,7 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
     if (sens) hipLaunchKernelGGL(lafse3::ipm_kernel_sens, dim3((unsigned)grid), dim3(64), 0, st, A, *sens);
     else if (sensx) hipLaunchKernelGGL(lafse3::ipm_kernel_sens_ex, dim3((unsigned)grid), dim3(64), 0, st, A, *sensx);
     else if (sensw) hipLaunchKernelGGL(lafse3::ipm_kernel_sens_w, dim3((unsigned)grid), dim3(64), 0, st, A, *sensw);
+    else if (rec) hipLaunchKernelGGL(lafse3::ipm_kernel_rec, dim3((unsigned)grid), dim3(64), 0, st, A, *rec);
     else if ((A.dump || c->rdump.buf) && A.mode == lafse3::MODE_SOLVE && !A.sched)
         hipLaunchKernelGGL(lafse3::ipm_kernel_dump, dim3((unsigned)grid), dim3(64), 0, st, A, c->rdump);
     else hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
@@ -409,12 +410,13 @@ static lafse3::KernelArgs blank_args()
     return A;
 }
 
-// lafse3_ocp_solve and, with sens, sensx or sensw, lafse3_ocp_sensitivity / _ex / _w: the one place that fills the
-// MODE_SOLVE arguments
+// lafse3_ocp_solve and, with sens, sensx, sensw or rec, lafse3_ocp_sensitivity / _ex / _w / lafse3_ocp_solve_rec: the one
+// place that fills the MODE_SOLVE arguments
 static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
                  const double *a_tra, const double *t, const double *u_last, double *x, double *u, double *lam,
                  double *cost, int32_t *status, int32_t *iters, void *stream, const lafse3::SensArgs *sens,
-                 const lafse3::SensExArgs *sensx = nullptr, const lafse3::SensWArgs *sensw = nullptr)
+                 const lafse3::SensExArgs *sensx = nullptr, const lafse3::SensWArgs *sensw = nullptr,
+                 const lafse3::RecArgs *rec = nullptr)
 {
     if (const int rc = check_call(c, B, {ini, goal, p_tra, a_tra, t})) return rc;
     if (B == 0) return LAFSE3_OK;
@@ -425,7 +427,7 @@ static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal
     A.n_inst = B;
     A.ini = ini; A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;
     A.x_out = x; A.u_out = u; A.lam_out = lam; A.cost_out = cost; A.status_out = status; A.iters_out = iters;
-    return launch(c, A, (hipStream_t)stream, 0, sens, sensx, sensw);
+    return launch(c, A, (hipStream_t)stream, 0, sens, sensx, sensw, rec);
 }
 
 int lafse3_ocp_solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
@@ -514,6 +516,60 @@ int lafse3_ocp_sensitivity_w(lafse3_ctx *c, int64_t B, const double *ini, const 
     Z.groups = sens ? groups : 0;   // a plain solve with per-instance weights ignores groups
     return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr, nullptr,
                  &Z);
+}
+
+int lafse3_rec_width(void) { return lafse3::REC_W; }
+
+int lafse3_ocp_solve_rec(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
+                         const double *a_tra, const double *t, const double *u_last, const double *weights, double *x,
+                         double *u, double *lam, double *cost, int32_t *status, int32_t *iters, double *rec,
+                         void *stream)
+{
+    if (!c) return fail(LAFSE3_EINVAL, "bad ctx / batch");
+    if (!rec) return fail(LAFSE3_EINVAL, "lafse3_ocp_solve_rec: rec is required");
+    lafse3::RecArgs Z;
+    Z.weights = weights;
+    Z.rec = rec;
+    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr, nullptr,
+                 nullptr, &Z);
+}
+
+// Not a solver launch (as trajectory scoring in launch()): its queue head is word 3 of the scoring counter block, and
+// the solver block, the timing events and the error word of the last solver launch are left alone.
+int lafse3_ocp_vjp(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
+                   const double *a_tra, const double *t, const double *u_last, const double *weights,
+                   const double *rec, const double *g_x, const double *g_u, int32_t groups, double *grad,
+                   int32_t *sens_status, void *stream)
+{
+    if (!c) return fail(LAFSE3_EINVAL, "bad ctx / batch");
+    if (groups == 0 || (groups & ~lafse3::SENS_W_ALL))
+        return fail(LAFSE3_EINVAL, "lafse3_ocp_vjp: groups must be a non-empty subset of "
+                                   "LAFSE3_SENS_THETA | LAFSE3_SENS_INI | LAFSE3_SENS_GOAL | LAFSE3_SENS_WEIGHTS");
+    if (!rec || !grad) return fail(LAFSE3_EINVAL, "lafse3_ocp_vjp: rec and grad are required");
+    if (const int rc = check_call(c, B, {ini, goal, p_tra, a_tra, t})) return rc;
+    if (B == 0) return LAFSE3_OK;
+    DeviceGuard dev(c->device);
+    if (dev.err != hipSuccess) return fail(LAFSE3_EDEVICE, "hipSetDevice", dev.err);
+    const int64_t grid = B < c->slots ? B : c->slots;
+    if (const int rc = reserve_ws(c, grid)) return rc;
+    lafse3::VjpArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.prm = c->prm;
+    A.n_inst = B;
+    A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;   // ini_state: stage 0 of the record
+    A.weights = weights;
+    A.rec = rec; A.gx = g_x; A.gu = g_u;
+    A.grad = grad; A.sens_out = sens_status; A.groups = groups;
+    A.counters = c->counters.data() + N_COUNTERS;
+    A.ws = c->ws.data();
+    hipStream_t st = (hipStream_t)stream;
+    // the queue head alone: the kernel touches no other word of the block
+    hipError_t e = hipMemsetAsync(A.counters + 3, 0, sizeof(unsigned long long), st);
+    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "hipMemsetAsync", e);
+    hipLaunchKernelGGL(lafse3::vjp_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(LAFSE3_EDEVICE, "vjp kernel launch", e);
+    return LAFSE3_OK;
 }
 
 // ---- fp32 twin of lafse3_ocp_solve: float inputs/outputs at the boundary, fp64 arithmetic inside (IPOPT's

@@ -200,6 +200,19 @@ struct SensWArgs {
     int32_t *sens_out;              // as SensArgs::sens_out
     int32_t groups;                 // LAFSE3_SENS_THETA | _INI | _GOAL | _WEIGHTS
 };
+// The optimum record of lafse3_ocp_solve_rec (read back by vjp.inc): dump_point's iterate block
+// x | u | lam | zLu | zUu | zLw | zUw, stage-major and padded to MAXN, then four scalars
+constexpr int REC_X = 0, REC_U = REC_X + (MAXN + 1) * NX, REC_LAM = REC_U + MAXN * NU, REC_ZLU = REC_LAM + MAXN * NX;
+constexpr int REC_ZUU = REC_ZLU + MAXN * NU, REC_ZLW = REC_ZUU + MAXN * NU, REC_ZUW = REC_ZLW + (MAXN + 1) * 3;
+constexpr int REC_MU = REC_ZUW + (MAXN + 1) * 3, REC_S = REC_MU + 1, REC_STATUS = REC_S + 1, REC_N = REC_STATUS + 1;
+constexpr int REC_W = REC_N + 1;
+static_assert(REC_MU == DUMP_W - DUMP_STEP_W, "the record's arrays are dump_point's iterate block");
+static_assert(REC_W == 2223, "lafse3.h documents the optimum record as 2223 doubles per instance");
+// second argument of ipm_kernel_rec: per-instance weights as SensWArgs, and the record
+struct RecArgs {
+    const double *weights;          // B x LAFSE3_NW cost weights, lafse3_params order (nullable: the context's)
+    double *rec;                    // B x REC_W
+};
 
 struct Ctl {
     int N;
@@ -508,6 +521,19 @@ __device__ __noinline__ void dump_point(const Smem &S, const gdouble *ws, int N,
     for (int e = lane; e < (N + 1) * 3; e += WAVE) {
         out[e] = ZLW[(e % 3) * SX + e / 3];
         out[(MAXN + 1) * 3 + e] = ZUW[(e % 3) * SX + e / 3];
+    }
+}
+
+// The optimum record of one instance (REC_*): the point the sensitivity passes factorise at, written by
+// ipm_kernel_rec only (run_instance<.., RECORD>) after the ordinary outputs.  The scalars are stores of lane 0.
+__device__ __noinline__ void rec_store(const Smem &S, const gdouble *ws, int status, double *out)
+{
+    dump_point(S, ws, S.C.N, out);
+    if (lane_id() == 0) {
+        out[REC_MU] = S.C.mu;
+        out[REC_S] = S.C.s;
+        out[REC_STATUS] = (double)status;
+        out[REC_N] = (double)S.C.N;
     }
 }
 
@@ -1876,12 +1902,15 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 // SENSX (ipm_kernel_sens_ex): the pass of sens_ex.inc follows a MODE_SOLVE instance, as SENS.
 // SENSW (ipm_kernel_sens_w): the instance's ten cost weights come from ZW->weights (MODE_SOLVE only) and the pass of
 // sens_w.inc follows.
-template <bool SENS, bool DUMP = false, bool SENSX = false, bool SENSW = false>
+// RECORD (ipm_kernel_rec, with SENSW): the weights come from ZC->weights, no pass follows, and the optimum record is stored
+// after the ordinary outputs (rec_store).
+template <bool SENS, bool DUMP = false, bool SENSX = false, bool SENSW = false, bool RECORD = false>
 __device__ __attribute__((always_inline)) inline int run_instance(const KernelArgs &A, Smem &S, const int64_t inst,
                                                                  gdouble *ws, const SensArgs *Z = nullptr,
                                                                  const SensExArgs *ZX = nullptr,
                                                                  const SensWArgs *ZW = nullptr,
-                                                                 const RestoDumpArgs *ZR = nullptr)
+                                                                 const RestoDumpArgs *ZR = nullptr,
+                                                                 const RecArgs *ZC = nullptr)
 {
     const int lane = lane_id();
     const lafse3_params &prm = A.prm;
@@ -1894,9 +1923,12 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
     if constexpr (SENSW) {
         w_peak = prm.tra_w_peak;
         w_decay = prm.tra_w_decay;
-        if (ZW->weights) {
+        const double *wts;
+        if constexpr (RECORD) wts = ZC->weights;
+        else wts = ZW->weights;
+        if (wts) {
             // used as given (include/lafse3.h): everything downstream reads M and S.wk
-            const double *w = ZW->weights + inst * (int64_t)NW;
+            const double *w = wts + inst * (int64_t)NW;
             M.wrt = w[W_WRT]; M.wqt = w[W_WQT]; M.wthrust = w[W_WTHRUST]; M.wrf = w[W_WRF]; M.wvf = w[W_WVF];
             M.wqf = w[W_WQF]; M.wwf = w[W_WWF]; M.du_w = w[W_DU];
             w_peak = w[W_PEAK];
@@ -2585,7 +2617,7 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
             if (lane == 0 && ZX->sens_out) ZX->sens_out[inst] = sst;
         }
     }
-    if constexpr (SENSW) {
+    if constexpr (SENSW && !RECORD) {
         if (A.mode == MODE_SOLVE && (ZW->dx_out || ZW->du_out || ZW->gain_out)) {
             const int64_t P = sens_w_columns(ZW->groups);
             const int sst = sens_w_pass(prm, M, S, C, ws, a3, tt, w_decay, status <= 1, ZW->groups,
@@ -2595,6 +2627,7 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
             if (lane == 0 && ZW->sens_out) ZW->sens_out[inst] = sst;
         }
     }
+    if constexpr (RECORD) rec_store(S, ws, status, ZC->rec + inst * (int64_t)REC_W);
     PT_END(S, 10);
 #ifdef LAFSE3_PHASE_TIMERS
     if (A.ptime && lane < 16) A.ptime[inst * PT_COLS + lane] = S.pt[lane];
@@ -2839,6 +2872,27 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_sens_w(KernelArgs A, SensWAr
         run_instance<false, false, false, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, nullptr, &Z);
     }
 }
+
+// The persistent solver with per-instance cost weights that also stores the optimum record (lafse3_ocp_solve_rec only):
+// run_instance<.., SENSW, RECORD> in a kernel of its own with the plain queue-head loop and its own argument struct.
+__global__ __launch_bounds__(64, 1) void ipm_kernel_rec(KernelArgs A, RecArgs Z)
+{
+    Smem &S = instance_smem();
+    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
+    for (;;) {
+        unsigned long long v = 0ull;
+        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
+        const int64_t inst = bcast_i64((int64_t)v);
+        if (inst >= A.n_inst) break;
+        typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
+        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+        __asm__ volatile("" : "+s"(Ap));
+        run_instance<false, false, false, true, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, nullptr, nullptr,
+                                                      nullptr, &Z);
+    }
+}
+
+#include "vjp.inc"
 
 // out8 from the 9 rewards per sample (quad_policy.py:97-112)
 __global__ void assemble_kernel(int64_t B, const double *R9, const float *dnn, double *out8)

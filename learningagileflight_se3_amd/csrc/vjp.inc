@@ -1,0 +1,245 @@
+// vjp.inc — one-sweep adjoint of the optimum's sensitivities from a saved optimum record (lafse3_ocp_vjp; #included by
+// ipm_kernel.hip after the solver kernels; vjp_kernel is no instantiation of run_instance).
+//
+//   grad[q] = sum_k g_x[k] . dx*_k/dparam_q + sum_k g_u[k] . du*_k/dparam_q      for every selected column q
+//
+// The forward route (sens_w.inc) computes dz*/dparam_q = -K^{-1} c_q with one sweep per column.  K is symmetric, so
+//   g^T (-K^{-1} c_q) = (-K^{-1} g)^T c_q = d . c_q,       d = the sweep on the right-hand side r = g,
+// which is sens_ex.inc's adjoint route with the unit vector e_(u_0, a) replaced by the incoming gradient: g_x of
+// stages 1..N in the x rows (WS_RQ), g_u in the u rows (WS_RR), zero in the dynamics rows (WS_RC).  One factorisation
+// and one sweep per instance for any number of columns; the contraction is the gain block of sens_w_pass (x rows
+// against DX, u rows against DU, the ini_state group through At_times on lam+_0 plus the qu term).  Stage 0 is not a
+// decision variable: dx_0/dini_state is the identity, so g_x[0] is added to the ini_state columns directly.
+//
+// The point comes from the record ipm_kernel_rec stored (REC_*), not from a solve on this wave: the instance prologue
+// of run_instance (Model and the weight row, attitude forms, S.wk, relaxed bounds, init_gv_const, goal / p_tra /
+// u_last) is repeated here from the same arguments, then x, u, the scaled lam, the bound duals, mu and the objective
+// scaling are loaded.  It is repeated, not shared: run_instance stays the code it is.
+constexpr int VJP_HORIZON = 3;   // sens_status: the record's horizon is not the context's
+
+struct VjpArgs {
+    lafse3_params prm;
+    int64_t n_inst;
+    const double *goal, *ptra, *atra, *t, *ulast;   // as KernelArgs (ini_state is stage 0 of the record's x)
+    const double *weights;                          // B x LAFSE3_NW or null, as SensWArgs
+    const double *rec;                              // B x REC_W
+    const double *gx, *gu;                          // B x (N+1) x 13, B x N x 4 (each nullable: zero)
+    double *grad;                                   // B x P
+    int32_t *sens_out;                              // B (nullable)
+    int32_t groups;                                 // LAFSE3_SENS_THETA | _INI | _GOAL | _WEIGHTS
+    unsigned long long *counters;                   // [3] the work-queue head
+    double *ws;
+};
+
+__device__ __attribute__((always_inline)) inline void vjp_instance(const VjpArgs &A, Smem &S, const int64_t inst,
+                                                                   gdouble *ws)
+{
+    const int lane = lane_id();
+    const lafse3_params &prm = A.prm;
+    const int N = prm.horizon;
+    const int groups = A.groups;
+    const int P = sens_w_columns(groups);
+    const double *rec = A.rec + inst * (int64_t)REC_W;
+    double *o = A.grad + inst * (int64_t)P;
+    // the scalars first: nothing is read by horizon from a record of another horizon
+    int st = SENS_OK;
+    if (!(rec[REC_STATUS] >= 0.0 && rec[REC_STATUS] <= 1.0)) st = SENS_UNCONVERGED;
+    if (!(rec[REC_N] == (double)N)) st = VJP_HORIZON;
+    st = __builtin_amdgcn_readfirstlane(st);   // every lane read the same words: uniform for the compiler too
+
+    if (st == SENS_OK) {
+        // ---- instance prologue (run_instance, MODE_SOLVE with SENSW)
+        Model &M = S.mdl;
+        M = make_model(prm);
+        double w_peak = prm.tra_w_peak, w_decay = prm.tra_w_decay;
+        if (A.weights) {
+            const double *w = A.weights + inst * (int64_t)NW;
+            M.wrt = w[W_WRT]; M.wqt = w[W_WQT]; M.wthrust = w[W_WTHRUST]; M.wrf = w[W_WRF]; M.wvf = w[W_WVF];
+            M.wqf = w[W_WQF]; M.wwf = w[W_WWF]; M.du_w = w[W_DU];
+            w_peak = uniform(w[W_PEAK]);
+            w_decay = uniform(w[W_DECAY]);
+        }
+        init_gv_const(M, S);
+        WS_TRAJ(ws);
+        // Whatever the contraction at the end reads of this prologue is wave-uniform and kept in SGPRs (uniform()), or
+        // in LDS: the loops below retire their lanes one by one, and the compiler has parked vector registers that
+        // live across such a loop in AGPRs at its exit before the lanes were switched on again (tra_w_decay and
+        // dt k - t came back as garbage in the weight columns).  The contraction forms its per-lane values afresh.
+        double p3[3], a3[3], q4[4];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            p3[i] = uniform(A.ptra[inst * 3 + i]);
+            a3[i] = uniform(A.atra[inst * 3 + i]);
+        }
+        const double tt = uniform(A.t[inst]);
+        rd2quat(magni3(a3), a3, q4);
+        Ctl &C = S.C;
+        C.N = N;
+        C.ulo = prm.u_lb - prm.bound_relax * fmax(1.0, fabs(prm.u_lb));
+        C.uhi = prm.u_ub + prm.bound_relax * fmax(1.0, fabs(prm.u_ub));
+        C.wlo = prm.w_lb - prm.bound_relax * fmax(1.0, fabs(prm.w_lb));
+        C.whi = prm.w_ub + prm.bound_relax * fmax(1.0, fabs(prm.w_ub));
+        C.s = uniform(rec[REC_S]);
+        C.mu = uniform(rec[REC_MU]);
+#ifdef LAFSE3_PHASE_TIMERS
+        S.timing = 0;
+#endif
+#ifdef LAFSE3_FAC_CHECK
+        if (lane < 4) S.facd[lane] = 0.0;
+#endif
+        if (lane < 3) {
+            S.goal[lane] = A.goal[inst * 3 + lane];
+            S.ptra[lane] = p3[lane];
+        }
+        if (lane < 4) S.ulast[lane] = A.ulast ? A.ulast[inst * 4 + lane] : 0.0;
+        Attitude &at = S.at;
+        {
+            double Rt[9], Rg[9], St[16], Sg[16];
+            dcm(q4, Rt);
+            attitude_form(Rt, St);
+            const double qg[4] = {1, 0, 0, 0};
+            dcm(qg, Rg);
+            attitude_form(Rg, Sg);
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    at.St[i] = St[i];
+                    at.Sg[i] = Sg[i];
+                }
+                at.trRt = Rt[0] + Rt[4] + Rt[8];
+                at.trRg = Rg[0] + Rg[4] + Rg[8];
+            }
+        }
+        // ---- the record: stage-major [k][i] -> SoA [i][k]; every index is below the block's (N+1) or N rows
+        for (int e = lane; e < (N + 1) * NX; e += WAVE) S.x[(e % NX) * SX + e / NX] = rec[REC_X + e];
+        for (int e = lane; e < N * NU; e += WAVE) {
+            S.u[(e % NU) * SX + e / NU] = rec[REC_U + e];
+            ZLU[(e % NU) * SX + e / NU] = rec[REC_ZLU + e];
+            ZUU[(e % NU) * SX + e / NU] = rec[REC_ZUU + e];
+        }
+        for (int e = lane; e < N * NX; e += WAVE) LAM[(e % NX) * SX + e / NX] = rec[REC_LAM + e];
+        for (int e = lane; e < (N + 1) * 3; e += WAVE) {
+            ZLW[(e % 3) * SX + e / 3] = rec[REC_ZLW + e];
+            ZUW[(e % 3) * SX + e / 3] = rec[REC_ZUW + e];
+        }
+        for (int e = lane; e < NX * SX; e += WAVE) {
+            DX[e] = 0.0;
+            LP[e] = 0.0;
+        }
+        for (int e = lane; e < NU * SX; e += WAVE) DU[e] = 0.0;
+        if (lane <= N) {
+            const double dtk = prm.dt * lane - tt;
+            S.wk[lane] = w_peak * exp(-w_decay * dtk * dtk);   // run_instance's expression
+        }
+        vm_sync();
+
+        // ---- factorise at the recorded point, as sens_w_pass does
+        int sw = 0;
+        double rat[4];
+        if (!linear_solve(M, S.at, S, C, ws, 0.0, 1, 0, 0, 0, sw, rat, nullptr)) st = SENS_INERTIA;
+        if (st == SENS_OK) {
+            // ---- right-hand side: g_x of stages 1..N in the x rows, g_u in the u rows, no dynamics rows
+            gdouble *rq = ws + WS_RQ, *rr = ws + WS_RR, *rc = ws + WS_RC;
+            const double *gx = A.gx ? A.gx + inst * (int64_t)(N + 1) * NX : nullptr;
+            const double *gu = A.gu ? A.gu + inst * (int64_t)N * NU : nullptr;
+            for (int e = lane; e < NX * SX; e += WAVE) {
+                const int i = e / SX, k = e % SX;
+                rq[e] = (gx && k >= 1 && k <= N) ? gx[k * NX + i] : 0.0;
+                rc[e] = 0.0;
+            }
+            for (int e = lane; e < NU * SX; e += WAVE) {
+                const int a = e / SX, k = e % SX;
+                rr[e] = (gu && k < N) ? gu[k * NU + a] : 0.0;
+            }
+            vm_sync();
+            linear_solve(M, S.at, S, C, ws, 0.0, 0, 0, 0, 0, sw, rat, nullptr);
+            sync();
+            // ---- contraction with dF/dparam_q, column by column (the gain block of sens_w_pass)
+            // nothing per-lane is carried over from before the sweep (see above); the mask keeps the index's range
+            // known, which the shared inline helpers' compares are specialised on in every kernel
+            const int lane = opaque_lane() & (WAVE - 1);
+            lafse3_params pw;   // sens_column's t column reads dt and tra_w_decay: the instance's decay
+            pw.dt = prm.dt;
+            pw.tra_w_decay = w_decay;
+            int col = 0;
+            for (int grp = SENS_G_THETA; grp <= SENS_G_W; grp <<= 1) {
+                if (!(groups & grp)) continue;
+                if (grp == SENS_G_INI) {
+                    // stage 0 only: (A_0^T lam+_0)_i + qu_i (du_0[0] + .. + du_0[3]), plus g_x[0][i] for dx_0 = identity
+                    double x0[NX], u0[NU], l0[NX], lp0[NX], atl[NX];
+                    load_stage(S, 0, x0);
+                    load_u(S, 0, u0);
+#pragma unroll
+                    for (int i = 0; i < NX; ++i) {
+                        l0[i] = LAM[i * SX];
+                        lp0[i] = LP[i * SX];
+                    }
+                    At_times(M, x0, u0, lp0, atl);
+                    StageHess H;
+                    stage_hessian(M, S.at, C.s, 0.0, x0, u0, l0, H);
+                    double sdu = 0.0;
+#pragma unroll
+                    for (int b = 0; b < NU; ++b) sdu += DU[b * SX];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) atl[6 + i] += H.qu[i] * sdu;
+                    if (lane < NX) {
+                        double v = atl[0];
+#pragma unroll
+                        for (int i = 1; i < NX; ++i) v = (lane == i) ? atl[i] : v;
+                        o[col + lane] = v + (gx ? gx[lane] : 0.0);
+                    }
+                    col += NX;
+                    continue;
+                }
+                const int nq = sens_w_group_size(grp);
+                for (int q = 0; q < nq; ++q, ++col) {
+                    double acc = 0.0;
+                    if (grp == SENS_G_W) {
+                        if (lane <= N) {   // x rows k = 1..N against dx, u rows k = 0..N-1 against du
+                            const int k = lane;
+                            double vx[NX], vu[NU];
+                            sens_w_column(M, S, C, prm.dt, w_decay, tt, q, k, vx, vu);
+                            if (k >= 1) {
+#pragma unroll
+                                for (int i = 0; i < NX; ++i) acc = fma(DX[i * SX + k], vx[i], acc);
+                            }
+                            if (k < N) {
+#pragma unroll
+                                for (int b = 0; b < NU; ++b) acc = fma(DU[b * SX + k], vu[b], acc);
+                            }
+                        }
+                    } else if (lane >= 1 && lane <= N) {   // theta and goal columns have x rows only
+                        const int k = lane;
+                        double vx[NX], vu[NU], vc[NX];
+                        sens_column(pw, M, S, C, a3, tt, grp, q, k, vx, vu, vc);
+#pragma unroll
+                        for (int i = 0; i < NX; ++i) acc = fma(DX[i * SX + k], vx[i], acc);
+                    }
+                    acc = wsum(acc);
+                    if (lane == 0) o[col] = acc;
+                }
+            }
+        }
+    }
+    if (st != SENS_OK)
+        for (int e = lane; e < P; e += WAVE) o[e] = 0.0;
+    if (lane == 0 && A.sens_out) A.sens_out[inst] = st;
+    sync();   // the next instance's prologue writes the LDS this one's last lanes may still read
+}
+
+// One wave per instance, the persistent queue-head loop and workspace slots of ipm_kernel_sens_w.
+__global__ __launch_bounds__(64, 1) void vjp_kernel(VjpArgs A)
+{
+    Smem &S = instance_smem();
+    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
+    for (;;) {
+        unsigned long long v = 0ull;
+        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
+        const int64_t inst = bcast_i64((int64_t)v);
+        if (inst >= A.n_inst) break;
+        typedef const VjpArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
+        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+        __asm__ volatile("" : "+s"(Ap));
+        vjp_instance(*(const VjpArgs *)Ap, S, inst, ws);
+    }
+}

@@ -19,6 +19,11 @@ a constant throughout.
 With ``weights=`` (the ten cost weights per instance, ``Engine.ocp_sensitivity_w``) both layers solve each instance
 under its own weights and send a gradient to them: the derivative with respect to the learnable parameters of the
 cost.  Without it they are the functions above, with the same launches.
+
+``mpc_layer(..., backward="adjoint")`` keeps the optimum instead of its Jacobians: the forward pass is one
+``Engine.ocp_solve_rec`` launch that saves the primal-dual point (about 18 KB per instance), and ``backward()`` is one
+``Engine.ocp_vjp`` launch that factorises there and sweeps once on the incoming gradient (K is symmetric, so
+g^T K^{-1} c_q for every column q costs one solve with g).  The default route stores B x P x 863 doubles and runs P sweeps.
 """
 from __future__ import annotations
 
@@ -233,15 +238,63 @@ class MPCPolicyFunctionW(torch.autograd.Function):
         return (None, *gr[:5], None, gr[5])
 
 
+class MPCFunctionAdj(torch.autograd.Function):
+    """The adjoint route of MPCFunctionW: (engine, ini_state, goal, p_tra, a_tra, t, u_last, weights) -> (x, u, status)
+    with the same gradients, computed at ``backward()`` time instead of stored at forward time.
+
+    forward is one ``Engine.ocp_solve_rec`` launch; it saves the optimum record (``Engine.rec_width()`` doubles per
+    instance) and its inputs, never dx or du.  backward is one ``Engine.ocp_vjp`` launch, one factorisation and one
+    sweep per instance, for the parameter groups with an input that needs a gradient.  ``weights`` may be None (the
+    context's weights, no gradient).  ``backward()`` may be called again with ``retain_graph``.  Double backward is
+    not supported: the gradients are returned as constants."""
+
+    @staticmethod
+    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights):
+        inputs = (ini_state, goal, p_tra, a_tra, t, u_last, weights)
+        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
+        ctx.groups = _needed_groups(needs, _GROUPS_W)
+        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t, weights))
+        out = engine.ocp_solve_rec(ini_state, goal, p_tra, a_tra, t, u_last, weights=weights, want=("x", "u"))
+        if ctx.groups:
+            ctx.engine = engine
+            # the tensors among the inputs are saved as such, the others (numpy, floats, None) kept as they are
+            ctx.is_tensor = tuple(isinstance(v, torch.Tensor) for v in inputs)
+            ctx.plain = tuple(None if s else v for v, s in zip(inputs, ctx.is_tensor))
+            ctx.save_for_backward(out["rec"], *(v for v, s in zip(inputs, ctx.is_tensor) if s))
+        ctx.mark_non_differentiable(out["status"])
+        return out["x"], out["u"], out["status"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_x, g_u, _g_status):
+        rec, *saved = ctx.saved_tensors
+        saved = iter(saved)
+        inputs = [next(saved) if s else v for v, s in zip(ctx.plain, ctx.is_tensor)]
+        res = ctx.engine.ocp_vjp(*inputs, rec, g_x, g_u, groups=ctx.groups)
+        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
+        gr = _scatter_columns(res["grad"], ctx.groups, ctx.metas, needs, _GROUPS_W)
+        return (None, *gr[:5], None, gr[5])
+
+
 def _wants_grad(v):
     return isinstance(v, torch.Tensor) and v.requires_grad
 
 
-def mpc_layer(engine, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None):
+def mpc_layer(engine, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None, backward="jacobian"):
     """Differentiable batched MPC solve -> (x, u, status); see MPCFunction.  When ini_state or goal is a tensor that
     requires a gradient, the solve goes through MPCFunctionEx, which also returns gradients to them.  ``weights``
     ((B, 10) or (10,), the cost weights of each instance): the solve goes through MPCFunctionW, and a ``weights`` that
-    requires a gradient receives one."""
+    requires a gradient receives one.
+
+    ``backward``: "jacobian" (the default) is those three functions, which store dx*/dparam and du*/dparam of every
+    selected column at forward time (B x P x 863 doubles) and contract them in ``backward()``.  "adjoint" selects
+    MPCFunctionAdj for any combination of inputs and weights: the forward launch saves the optimum itself (about 18 KB
+    per instance for any P) and ``backward()`` runs one adjoint sweep per instance.  Same gradients up to rounding;
+    double backward is not supported on the adjoint route."""
+    if backward == "adjoint":
+        return MPCFunctionAdj.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
+    if backward != "jacobian":
+        raise ValueError(f'backward: expected "jacobian" or "adjoint", got {backward!r}')
     if weights is not None:
         return MPCFunctionW.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
     if _wants_grad(ini_state) or _wants_grad(goal):

@@ -12,6 +12,7 @@ Reference interfaces mirrored (yanrui89/LearningAgileFlight_SE3):
   Engine.ocp_sensitivity  ocSolver + dx*/dtheta, du*/dtheta (the PDP auxiliary system sketched in quad_OC.py:214-306)
   Engine.ocp_sensitivity_ex  the same with ini_state and goal columns and the MPC feedback gain du*_0/dx_0
   Engine.ocp_sensitivity_w   the same with per-instance cost weights and the columns of the ten weights
+  Engine.ocp_solve_rec / ocp_vjp   the solve that saves its optimum, and a loss's gradients from it in one adjoint sweep
 """
 from __future__ import annotations
 
@@ -97,6 +98,40 @@ def _param_override(eng, field, value):
     finally:
         setattr(eng.params, field, saved)
         eng.set_params(eng.params)
+
+
+def _groups_w(groups, required=True):
+    """``groups`` of the calls with the four parameter groups (names of _lib.SENS_GROUPS_W, one name, or the
+    LAFSE3_SENS_* bit mask) -> (mask, column names in the fixed order).  ``required``: an empty selection or a bit
+    outside the four groups raises ValueError."""
+    G = _lib.SENS_GROUPS_W
+    if isinstance(groups, str):
+        groups = (groups,)
+    if isinstance(groups, int):
+        mask = int(groups)
+    else:
+        unknown = [g for g in groups if g not in G]
+        if unknown:
+            raise ValueError(f"groups: unknown {unknown}; expected any of {list(G)}")
+        mask = sum(bit for g, bit in G.items() if g in groups)
+    if required and (mask == 0 or mask & ~sum(G.values())):
+        raise ValueError(f"groups: {groups!r} selects no column or a bit outside {G}")
+    return mask, [c for g, bit in G.items() if mask & bit for c in _lib.SENS_COLUMNS_W[g]]
+
+
+def _weight_rows(weights, B, device):
+    """``weights`` (B, 10) or (10,) (broadcast over the batch) as a contiguous (B, 10) float64 tensor on ``device``;
+    None stays None (the context's weights)."""
+    if weights is None:
+        return None
+    w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights))
+    w = w.detach().to(device=device, dtype=torch.float64)
+    given = tuple(w.shape)
+    if given == (_lib.NW,):
+        w = w.unsqueeze(0).expand(B, _lib.NW)
+    if tuple(w.shape) != (B, _lib.NW):
+        raise ValueError(f"weights: expected ({B}, {_lib.NW}) or ({_lib.NW},), got {given}")
+    return w.contiguous()
 
 
 def _ptr(t):
@@ -358,33 +393,12 @@ class Engine:
         ``groups``: as ocp_sensitivity_ex plus "weights" (10 columns, last).  Returns ocp_sensitivity_ex's dict;
         ``columns`` ends with the ten weight names.  Without dx, du and gain in ``want`` the call is a plain solve
         with those weights.  float64 only."""
-        G = _lib.SENS_GROUPS_W
-        if isinstance(groups, str):
-            groups = (groups,)
-        if isinstance(groups, int):
-            mask = int(groups)
-        else:
-            unknown = [g for g in groups if g not in G]
-            if unknown:
-                raise ValueError(f"groups: unknown {unknown}; expected any of {list(G)}")
-            mask = sum(bit for g, bit in G.items() if g in groups)
         sens = any(k in want for k in ("dx", "du", "gain"))
-        if sens and (mask == 0 or mask & ~sum(G.values())):
-            raise ValueError(f"groups: {groups!r} selects no column or a bit outside {G}")
-        columns = [c for g, bit in G.items() if mask & bit for c in _lib.SENS_COLUMNS_W[g]]
+        mask, columns = _groups_w(groups, required=sens)
         P = len(columns)
         d, f64 = self.device, torch.float64
         B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
-        w = None
-        if weights is not None:
-            w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights))
-            w = w.detach().to(device=d, dtype=f64)
-            given = tuple(w.shape)
-            if given == (_lib.NW,):
-                w = w.unsqueeze(0).expand(B, _lib.NW)
-            if tuple(w.shape) != (B, _lib.NW):
-                raise ValueError(f"weights: expected ({B}, {_lib.NW}) or ({_lib.NW},), got {given}")
-            w = w.contiguous()
+        w = _weight_rows(weights, B, d)
         N = self.horizon
         shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,),
                   "dx": (B, P, N + 1, NX), "du": (B, P, N, NU), "gain": (B, NU, P)}
@@ -402,6 +416,63 @@ class Engine:
         res = {k: v for k, v in out.items() if v is not None}
         res["columns"] = columns
         return res
+
+    def rec_width(self) -> int:
+        """Doubles per instance of the optimum record (lafse3_rec_width; independent of the horizon)."""
+        return int(self._L.lafse3_rec_width())
+
+    def ocp_solve_rec(self, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None,
+                      want=("x", "u", "lam", "cost")):
+        """ocp_sensitivity_w as a plain solve that also saves its optimum (lafse3_ocp_solve_rec), one launch.
+
+        Returns ocp_solve's dict (x, u, lam, cost as named in ``want``; status, iters) plus
+          rec (B, rec_width()) float64: the primal-dual point the sensitivity passes factorise at (layout in
+          include/lafse3.h), which ``ocp_vjp`` turns into gradients later.  ``weights`` as ocp_sensitivity_w."""
+        d, f64 = self.device, torch.float64
+        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
+        w = _weight_rows(weights, B, d)
+        N = self.horizon
+        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,)}
+        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
+        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
+        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
+        # zeros: the entries of stages beyond the horizon are not written
+        out["rec"] = torch.zeros((B, self.rec_width()), dtype=f64, device=d)
+        check(self._L.lafse3_ocp_solve_rec(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
+                                           _ptr(w), _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]),
+                                           _ptr(out["cost"]), _ptr(out["status"]), _ptr(out["iters"]),
+                                           _ptr(out["rec"]), self._stream()), "lafse3_ocp_solve_rec")
+        return {k: v for k, v in out.items() if v is not None}
+
+    def ocp_vjp(self, ini_state, goal, p_tra, a_tra, t, u_last, weights, rec, g_x=None, g_u=None,
+                groups=("theta", "ini", "goal", "weights")):
+        """Gradients of a loss through the optimum from a saved record (lafse3_ocp_vjp), one small launch:
+          grad (B, P) = sum g_x dx*/dparam_q + sum g_u du*/dparam_q over the P columns of ``groups``
+        (ocp_sensitivity_w's groups and column order), by one factorisation and one adjoint sweep per instance.
+
+        The first seven arguments are those of the ``ocp_solve_rec`` call that returned ``rec`` (B, rec_width()),
+        under the same params.  g_x (B, N+1, 13), g_u (B, N, 4): the loss gradients w.r.t. x and u (None = zero).
+        Returns {grad, sens_status (B,) int32: 0 ok, 1 the recorded solve ended with status > 1, 2 wrong inertia at
+        the optimum, 3 the record's horizon is not this engine's (rows != 0 are zero), columns}.  float64 only."""
+        mask, columns = _groups_w(groups)
+        d, f64 = self.device, torch.float64
+        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
+        w = _weight_rows(weights, B, d)
+        N = self.horizon
+        if rec is None:
+            raise ValueError("rec is required")
+        rec = rec.detach().to(device=d, dtype=f64).contiguous()
+        if tuple(rec.shape) != (B, self.rec_width()):
+            raise ValueError(f"rec: expected ({B}, {self.rec_width()}), got {tuple(rec.shape)}")
+        gx = _dev_tensor(g_x, (N + 1, NX), f64, d, "g_x", allow_none=True)
+        gu = _dev_tensor(g_u, (N, NU), f64, d, "g_u", allow_none=True)
+        gx, gu = _same_batch(B, g_x=gx, g_u=gu)
+        grad = torch.empty((B, len(columns)), dtype=f64, device=d)
+        ss = torch.empty((B,), dtype=torch.int32, device=d)
+        check(self._L.lafse3_ocp_vjp(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
+                                     _ptr(w), _ptr(rec), _ptr(gx), _ptr(gu), mask, _ptr(grad), _ptr(ss),
+                                     self._stream()), "lafse3_ocp_vjp")
+        return {"grad": grad, "sens_status": ss, "columns": columns}
 
     def objective(self, ini_state, goal, gate12, p_tra, a_tra, t, u_last=None):
         """Batched run_quad.objective -> (reward (B,), status (B,))."""
