@@ -332,8 +332,7 @@ __global__ void slots_init_kernel(double *R, int32_t *S, int64_t n)
 }
 
 static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t sched_samples = 0,
-                  const lafse3::SensArgs *sens = nullptr, const lafse3::SensExArgs *sensx = nullptr,
-                  const lafse3::SensWArgs *sensw = nullptr, const lafse3::RecArgs *rec = nullptr)
+                  const lafse3::ExtArgs *ext = nullptr)
 {
     if (A.n_inst == 0) return LAFSE3_OK;
     // trajectory scoring (MODE_REWARD) counts nothing and has its own queue head: it leaves the last solver
@@ -387,12 +386,10 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
         return LAFSE3_OK;
     }
     (void)hipEventRecord(c->ev0, st);
-    // the sensitivity pass is compiled into a kernel of its own (ipm_kernel.hip ipm_kernel_sens)
-    // and so are the extra stores of a debug dump that carries the iterate (ipm_kernel_dump: plain solves only)
-    if (sens) hipLaunchKernelGGL(lafse3::ipm_kernel_sens, dim3((unsigned)grid), dim3(64), 0, st, A, *sens);
-    else if (sensx) hipLaunchKernelGGL(lafse3::ipm_kernel_sens_ex, dim3((unsigned)grid), dim3(64), 0, st, A, *sensx);
-    else if (sensw) hipLaunchKernelGGL(lafse3::ipm_kernel_sens_w, dim3((unsigned)grid), dim3(64), 0, st, A, *sensw);
-    else if (rec) hipLaunchKernelGGL(lafse3::ipm_kernel_rec, dim3((unsigned)grid), dim3(64), 0, st, A, *rec);
+    // per-instance weights, the sensitivity pass and the optimum record are compiled into a kernel of their own
+    // (ipm_kernel.hip ipm_kernel_ext), and so are the extra stores of a debug dump that carries the iterate
+    // (ipm_kernel_dump: plain solves only)
+    if (ext) hipLaunchKernelGGL(lafse3::ipm_kernel_ext, dim3((unsigned)grid), dim3(64), 0, st, A, *ext);
     else if ((A.dump || c->rdump.buf) && A.mode == lafse3::MODE_SOLVE && !A.sched)
         hipLaunchKernelGGL(lafse3::ipm_kernel_dump, dim3((unsigned)grid), dim3(64), 0, st, A, c->rdump);
     else hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
@@ -410,13 +407,11 @@ static lafse3::KernelArgs blank_args()
     return A;
 }
 
-// lafse3_ocp_solve and, with sens, sensx, sensw or rec, lafse3_ocp_sensitivity / _ex / _w / lafse3_ocp_solve_rec: the one
-// place that fills the MODE_SOLVE arguments
+// lafse3_ocp_solve and, with ext, lafse3_ocp_sensitivity / _ex / _w / lafse3_ocp_solve_rec: the one place that fills the
+// MODE_SOLVE arguments
 static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
                  const double *a_tra, const double *t, const double *u_last, double *x, double *u, double *lam,
-                 double *cost, int32_t *status, int32_t *iters, void *stream, const lafse3::SensArgs *sens,
-                 const lafse3::SensExArgs *sensx = nullptr, const lafse3::SensWArgs *sensw = nullptr,
-                 const lafse3::RecArgs *rec = nullptr)
+                 double *cost, int32_t *status, int32_t *iters, void *stream, const lafse3::ExtArgs *ext)
 {
     if (const int rc = check_call(c, B, {ini, goal, p_tra, a_tra, t})) return rc;
     if (B == 0) return LAFSE3_OK;
@@ -427,7 +422,7 @@ static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal
     A.n_inst = B;
     A.ini = ini; A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;
     A.x_out = x; A.u_out = u; A.lam_out = lam; A.cost_out = cost; A.status_out = status; A.iters_out = iters;
-    return launch(c, A, (hipStream_t)stream, 0, sens, sensx, sensw, rec);
+    return launch(c, A, (hipStream_t)stream, 0, ext);
 }
 
 int lafse3_ocp_solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
@@ -442,21 +437,21 @@ int lafse3_ocp_sensitivity(lafse3_ctx *c, int64_t B, const double *ini, const do
                            double *lam, double *cost, int32_t *status, int32_t *iters, double *dx, double *du,
                            int32_t *sens_status, void *stream)
 {
-    lafse3::SensArgs Z;
-    Z.dx_out = dx; Z.du_out = du; Z.sens_out = sens_status;
+    lafse3::ExtArgs Z = {};
+    Z.dx_out = dx; Z.du_out = du; Z.sens_out = sens_status; Z.groups = LAFSE3_SENS_THETA;
     // without dx and du the call is lafse3_ocp_solve
     return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream,
                  dx || du ? &Z : nullptr);
 }
 
 static_assert(LAFSE3_SENS_THETA == lafse3::SENS_G_THETA && LAFSE3_SENS_INI == lafse3::SENS_G_INI &&
-              LAFSE3_SENS_GOAL == lafse3::SENS_G_GOAL, "sens_ex.inc reads the header's group bits");
+              LAFSE3_SENS_GOAL == lafse3::SENS_G_GOAL, "sens.inc reads the header's group bits");
 
 int lafse3_sens_columns(int32_t groups)
 {
     if (groups & ~(LAFSE3_SENS_THETA | LAFSE3_SENS_INI | LAFSE3_SENS_GOAL))
         return fail(LAFSE3_EINVAL, "lafse3_sens_columns: bits outside LAFSE3_SENS_THETA | _INI | _GOAL");
-    return lafse3::sens_ex_columns(groups);
+    return lafse3::sens_columns(groups);
 }
 
 int lafse3_ocp_sensitivity_ex(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
@@ -471,13 +466,13 @@ int lafse3_ocp_sensitivity_ex(lafse3_ctx *c, int64_t B, const double *ini, const
     if (groups == 0 || (groups & ~(LAFSE3_SENS_THETA | LAFSE3_SENS_INI | LAFSE3_SENS_GOAL)))
         return fail(LAFSE3_EINVAL, "lafse3_ocp_sensitivity_ex: groups must be a non-empty subset of "
                                    "LAFSE3_SENS_THETA | LAFSE3_SENS_INI | LAFSE3_SENS_GOAL");
-    lafse3::SensExArgs Z;
+    lafse3::ExtArgs Z = {};
     Z.dx_out = dx; Z.du_out = du; Z.gain_out = gain; Z.sens_out = sens_status; Z.groups = groups;
-    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr, &Z);
+    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, &Z);
 }
 
 static_assert(LAFSE3_SENS_WEIGHTS == lafse3::SENS_G_W && LAFSE3_NW == lafse3::NW,
-              "sens_w.inc reads the header's weights group");
+              "sens.inc reads the header's weights group");
 // the ten weights are contiguous doubles of lafse3_params in the column order (weight_columns.hpp)
 static_assert(offsetof(lafse3_params, du_weight) - offsetof(lafse3_params, wrt) == (LAFSE3_NW - 1) * sizeof(double) &&
               offsetof(lafse3_params, tra_w_peak) - offsetof(lafse3_params, wrt) == lafse3::W_PEAK * sizeof(double),
@@ -487,7 +482,7 @@ int lafse3_sens_columns_w(int32_t groups)
 {
     if (groups & ~lafse3::SENS_W_ALL)
         return fail(LAFSE3_EINVAL, "lafse3_sens_columns_w: bits outside LAFSE3_SENS_THETA | _INI | _GOAL | _WEIGHTS");
-    return lafse3::sens_w_columns(groups);
+    return lafse3::sens_columns(groups);
 }
 
 int lafse3_params_weights(const lafse3_params *p, double w[LAFSE3_NW])
@@ -510,12 +505,11 @@ int lafse3_ocp_sensitivity_w(lafse3_ctx *c, int64_t B, const double *ini, const 
     if (sens && (groups == 0 || (groups & ~lafse3::SENS_W_ALL)))
         return fail(LAFSE3_EINVAL, "lafse3_ocp_sensitivity_w: groups must be a non-empty subset of "
                                    "LAFSE3_SENS_THETA | LAFSE3_SENS_INI | LAFSE3_SENS_GOAL | LAFSE3_SENS_WEIGHTS");
-    lafse3::SensWArgs Z;
+    lafse3::ExtArgs Z = {};
     Z.weights = weights;
     Z.dx_out = dx; Z.du_out = du; Z.gain_out = gain; Z.sens_out = sens_status;
     Z.groups = sens ? groups : 0;   // a plain solve with per-instance weights ignores groups
-    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr, nullptr,
-                 &Z);
+    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, &Z);
 }
 
 int lafse3_rec_width(void) { return lafse3::REC_W; }
@@ -527,11 +521,10 @@ int lafse3_ocp_solve_rec(lafse3_ctx *c, int64_t B, const double *ini, const doub
 {
     if (!c) return fail(LAFSE3_EINVAL, "bad ctx / batch");
     if (!rec) return fail(LAFSE3_EINVAL, "lafse3_ocp_solve_rec: rec is required");
-    lafse3::RecArgs Z;
+    lafse3::ExtArgs Z = {};
     Z.weights = weights;
     Z.rec = rec;
-    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, nullptr, nullptr,
-                 nullptr, &Z);
+    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, &Z);
 }
 
 // Not a solver launch (as trajectory scoring in launch()): its queue head is word 3 of the scoring counter block, and

@@ -173,32 +173,12 @@ struct KernelArgs {
     double *rws;                    // restoration-phase workspace, RWS_SIZE per slot
 };
 
-// second argument of ipm_kernel_sens (trajectory sensitivities, sens.inc).  Not part of KernelArgs: a larger
+// second argument of ipm_kernel_dump: the restoration dump (lafse3_debug_dump_resto).  Not part of KernelArgs: a larger
 // KernelArgs alone changed ipm_kernel's code (kernel-argument loads, register allocation).
-struct SensArgs {
-    double *dx_out, *du_out;        // B x 7 x (N+1) x 13, B x 7 x N x 4 (each nullable)
-    int32_t *sens_out;              // B: 0 ok, 1 the solve did not converge, 2 wrong inertia at z* (nullable)
-};
-// second argument of ipm_kernel_dump: the restoration dump (lafse3_debug_dump_resto).  Not part of KernelArgs, as SensArgs.
 struct RestoDumpArgs {
     double *buf;                    // RD_W doubles per instance (nullable)
     int entry, it;                  // the it-th iteration of the entry-th entry into the phase of each solve, 0-based
     int refine;                     // 0: the step before iterative refinement, 1: after
-};
-// second argument of ipm_kernel_sens_ex (sens_ex.inc): P = the columns of the selected groups
-struct SensExArgs {
-    double *dx_out, *du_out;        // B x P x (N+1) x 13, B x P x N x 4 (each nullable)
-    double *gain_out;               // B x 4 x P (nullable)
-    int32_t *sens_out;              // as SensArgs::sens_out
-    int32_t groups;                 // LAFSE3_SENS_THETA | _INI | _GOAL
-};
-// second argument of ipm_kernel_sens_w (sens_w.inc): SensExArgs with the weights group and the per-instance weights
-struct SensWArgs {
-    const double *weights;          // B x LAFSE3_NW cost weights, lafse3_params order (nullable: the context's)
-    double *dx_out, *du_out;        // B x P x (N+1) x 13, B x P x N x 4 (each nullable)
-    double *gain_out;               // B x 4 x P (nullable)
-    int32_t *sens_out;              // as SensArgs::sens_out
-    int32_t groups;                 // LAFSE3_SENS_THETA | _INI | _GOAL | _WEIGHTS
 };
 // The optimum record of lafse3_ocp_solve_rec (read back by vjp.inc): dump_point's iterate block
 // x | u | lam | zLu | zUu | zLw | zUw, stage-major and padded to MAXN, then four scalars
@@ -208,10 +188,15 @@ constexpr int REC_MU = REC_ZUW + (MAXN + 1) * 3, REC_S = REC_MU + 1, REC_STATUS 
 constexpr int REC_W = REC_N + 1;
 static_assert(REC_MU == DUMP_W - DUMP_STEP_W, "the record's arrays are dump_point's iterate block");
 static_assert(REC_W == 2223, "lafse3.h documents the optimum record as 2223 doubles per instance");
-// second argument of ipm_kernel_rec: per-instance weights as SensWArgs, and the record
-struct RecArgs {
+// second argument of ipm_kernel_ext (sens.inc, rec_store): per-instance weights, the sensitivity outputs over the P
+// columns of the selected groups, and the optimum record.  Not part of KernelArgs, as RestoDumpArgs.
+struct ExtArgs {
     const double *weights;          // B x LAFSE3_NW cost weights, lafse3_params order (nullable: the context's)
-    double *rec;                    // B x REC_W
+    double *dx_out, *du_out;        // B x P x (N+1) x 13, B x P x N x 4 (each nullable)
+    double *gain_out;               // B x 4 x P (nullable)
+    int32_t *sens_out;              // B: 0 ok, 1 the solve did not converge, 2 wrong inertia at z* (nullable)
+    int32_t groups;                 // LAFSE3_SENS_THETA | _INI | _GOAL | _WEIGHTS
+    double *rec;                    // B x REC_W (nullable)
 };
 
 struct Ctl {
@@ -525,7 +510,7 @@ __device__ __noinline__ void dump_point(const Smem &S, const gdouble *ws, int N,
 }
 
 // The optimum record of one instance (REC_*): the point the sensitivity passes factorise at, written by
-// ipm_kernel_rec only (run_instance<.., RECORD>) after the ordinary outputs.  The scalars are stores of lane 0.
+// ipm_kernel_ext only (run_instance<.., EXT> with ZE->rec) after the ordinary outputs.  The scalars are stores of lane 0.
 __device__ __noinline__ void rec_store(const Smem &S, const gdouble *ws, int status, double *out)
 {
     dump_point(S, ws, S.C.N, out);
@@ -1890,42 +1875,32 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 }
 
 #include "sens.inc"
-#include "sens_ex.inc"
-#include "sens_w.inc"
 
 // ------------------------------------------------------------------------------------------------
 // waves per SIMD the register allocation targets (LDS admits 2: Smem <= 20 KB)
 // One NLP instance (or one scored trajectory) on this wave, with the workspace slot ws.
 // Returns the instance's IPM iteration count (0 for trajectory scoring).
-// SENS (ipm_kernel_sens): the sensitivity pass of sens.inc follows a MODE_SOLVE instance; ipm_kernel compiles none of it.
 // DUMP (ipm_kernel_dump): the debug dump also records the iterate (dump_point); ipm_kernel compiles none of that.
-// SENSX (ipm_kernel_sens_ex): the pass of sens_ex.inc follows a MODE_SOLVE instance, as SENS.
-// SENSW (ipm_kernel_sens_w): the instance's ten cost weights come from ZW->weights (MODE_SOLVE only) and the pass of
-// sens_w.inc follows.
-// RECORD (ipm_kernel_rec, with SENSW): the weights come from ZC->weights, no pass follows, and the optimum record is stored
-// after the ordinary outputs (rec_store).
-template <bool SENS, bool DUMP = false, bool SENSX = false, bool SENSW = false, bool RECORD = false>
+// EXT (ipm_kernel_ext): the instance's ten cost weights come from ZE->weights (MODE_SOLVE only), the pass of sens.inc
+// follows a MODE_SOLVE instance when dx, du or gain is asked for, and the optimum record is stored after the ordinary
+// outputs when ZE->rec is set (rec_store); ipm_kernel compiles none of it.
+template <bool DUMP, bool EXT>
 __device__ __attribute__((always_inline)) inline int run_instance(const KernelArgs &A, Smem &S, const int64_t inst,
-                                                                 gdouble *ws, const SensArgs *Z = nullptr,
-                                                                 const SensExArgs *ZX = nullptr,
-                                                                 const SensWArgs *ZW = nullptr,
-                                                                 const RestoDumpArgs *ZR = nullptr,
-                                                                 const RecArgs *ZC = nullptr)
+                                                                 gdouble *ws, const ExtArgs *ZE = nullptr,
+                                                                 const RestoDumpArgs *ZR = nullptr)
 {
     const int lane = lane_id();
     const lafse3_params &prm = A.prm;
     Model &M = S.mdl;
     M = make_model(prm);   // every lane writes the same values: no barrier needed before its own reads
-    // SENSW: the traversal weight's shape of this instance (the other kernels read the context's where they use it)
+    // EXT: the traversal weight's shape of this instance (the other kernels read the context's where they use it)
     [[maybe_unused]] double w_peak = 0.0, w_decay = 0.0;
     // a non-finite weight need not reach the error norms (fmax drops a NaN): the instance ends as non-finite below
     [[maybe_unused]] bool w_nonfinite = false;
-    if constexpr (SENSW) {
+    if constexpr (EXT) {
         w_peak = prm.tra_w_peak;
         w_decay = prm.tra_w_decay;
-        const double *wts;
-        if constexpr (RECORD) wts = ZC->weights;
-        else wts = ZW->weights;
+        const double *wts = ZE->weights;
         if (wts) {
             // used as given (include/lafse3.h): everything downstream reads M and S.wk
             const double *w = wts + inst * (int64_t)NW;
@@ -2076,7 +2051,7 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
                 ZUW[c * SX + k] = (k >= 1) ? 1.0 : 0.0;
             }
             double dtk = prm.dt * k - tt;
-            if constexpr (SENSW) S.wk[k] = w_peak * exp(-w_decay * dtk * dtk);   // the same expression: the same bits
+            if constexpr (EXT) S.wk[k] = w_peak * exp(-w_decay * dtk * dtk);   // the same expression: the same bits
             else S.wk[k] = prm.tra_w_peak * exp(-prm.tra_w_decay * dtk * dtk);
         }
         if (lane < N) {
@@ -2179,7 +2154,7 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
         PT_END(S, 1);
         double e0 = err_value(E, 0);
         if (!isfinite(e0)) { status = ST_NONFINITE; break; }
-        if constexpr (SENSW)
+        if constexpr (EXT)
             if (w_nonfinite) { status = ST_NONFINITE; break; }
         if (e0 <= prm.tol && E.dinf / C.s <= 1.0 && E.pinf <= 1e-4 && E.c0 / C.s <= 1e-4) {
             status = ST_SOLVED;
@@ -2598,36 +2573,18 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
                 for (int q = 1; q <= 6; ++q) A.status_out[b * 9 + q] = pst;
         }
     }
-    if constexpr (SENS) {
+    if constexpr (EXT) {
         // after every ordinary output is stored: the optimum, the final mu and the bound duals are still in LDS / ws
-        if (A.mode == MODE_SOLVE && (Z->dx_out || Z->du_out)) {
-            const int sst = sens_pass(prm, M, S, C, ws, a3, tt, status <= 1,
-                                      Z->dx_out ? Z->dx_out + inst * (int64_t)SENS_NP * (N + 1) * NX : nullptr,
-                                      Z->du_out ? Z->du_out + inst * (int64_t)SENS_NP * N * NU : nullptr);
-            if (lane == 0 && Z->sens_out) Z->sens_out[inst] = sst;
+        if (A.mode == MODE_SOLVE && (ZE->dx_out || ZE->du_out || ZE->gain_out)) {
+            const int64_t P = sens_columns(ZE->groups);
+            const int sst = sens_pass(M, S, C, ws, a3, prm.dt, w_decay, tt, status <= 1, ZE->groups,
+                                      ZE->dx_out ? ZE->dx_out + inst * P * (N + 1) * NX : nullptr,
+                                      ZE->du_out ? ZE->du_out + inst * P * N * NU : nullptr,
+                                      ZE->gain_out ? ZE->gain_out + inst * NU * P : nullptr);
+            if (lane == 0 && ZE->sens_out) ZE->sens_out[inst] = sst;
         }
+        if (ZE->rec) rec_store(S, ws, status, ZE->rec + inst * (int64_t)REC_W);
     }
-    if constexpr (SENSX) {
-        if (A.mode == MODE_SOLVE && (ZX->dx_out || ZX->du_out || ZX->gain_out)) {
-            const int64_t P = sens_ex_columns(ZX->groups);
-            const int sst = sens_ex_pass(prm, M, S, C, ws, a3, tt, status <= 1, ZX->groups,
-                                         ZX->dx_out ? ZX->dx_out + inst * P * (N + 1) * NX : nullptr,
-                                         ZX->du_out ? ZX->du_out + inst * P * N * NU : nullptr,
-                                         ZX->gain_out ? ZX->gain_out + inst * NU * P : nullptr);
-            if (lane == 0 && ZX->sens_out) ZX->sens_out[inst] = sst;
-        }
-    }
-    if constexpr (SENSW && !RECORD) {
-        if (A.mode == MODE_SOLVE && (ZW->dx_out || ZW->du_out || ZW->gain_out)) {
-            const int64_t P = sens_w_columns(ZW->groups);
-            const int sst = sens_w_pass(prm, M, S, C, ws, a3, tt, w_decay, status <= 1, ZW->groups,
-                                        ZW->dx_out ? ZW->dx_out + inst * P * (N + 1) * NX : nullptr,
-                                        ZW->du_out ? ZW->du_out + inst * P * N * NU : nullptr,
-                                        ZW->gain_out ? ZW->gain_out + inst * NU * P : nullptr);
-            if (lane == 0 && ZW->sens_out) ZW->sens_out[inst] = sst;
-        }
-    }
-    if constexpr (RECORD) rec_store(S, ws, status, ZC->rec + inst * (int64_t)REC_W);
     PT_END(S, 10);
 #ifdef LAFSE3_PHASE_TIMERS
     if (A.ptime && lane < 16) A.ptime[inst * PT_COLS + lane] = S.pt[lane];
@@ -2794,33 +2751,15 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel(KernelArgs A)
         typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;
         KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         __asm__ volatile("" : "+s"(Ap));
-        const int it = run_instance<false>(*(const KernelArgs *)Ap, S, inst, ws);
+        const int it = run_instance<false, false>(*(const KernelArgs *)Ap, S, inst, ws);
         if (A.sched && inst < Bs) sched_push(A, Bs, inst, it);
     }
 }
 
-// The persistent solver with the sensitivity pass compiled in (lafse3_ocp_sensitivity only): a second instantiation
-// of run_instance in a kernel of its own, so that ipm_kernel's code is what it is without the pass.  Its launches are
-// always persistent MODE_SOLVE launches without a probe queue, so the loop is the plain queue-head loop.
-__global__ __launch_bounds__(64, 1) void ipm_kernel_sens(KernelArgs A, SensArgs Z)
-{
-    Smem &S = instance_smem();
-    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
-    for (;;) {
-        unsigned long long v = 0ull;
-        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
-        const int64_t inst = bcast_i64((int64_t)v);
-        if (inst >= A.n_inst) break;
-        typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
-        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-        __asm__ volatile("" : "+s"(Ap));
-        run_instance<true>(*(const KernelArgs *)Ap, S, inst, ws, &Z);
-    }
-}
-
 // The persistent solver whose debug dump carries the iterate (lafse3_debug_dump or lafse3_debug_dump_resto armed,
-// lafse3_ocp_solve launches): as ipm_kernel_sens a further instantiation of run_instance in a kernel of its own with the
-// plain queue-head loop, so that ipm_kernel's code is what it is without the extra stores.
+// lafse3_ocp_solve launches): a further instantiation of run_instance in a kernel of its own, so that ipm_kernel's code is
+// what it is without the extra stores.  Its launches are always persistent MODE_SOLVE launches without a probe queue, so
+// the loop is the plain queue-head loop.
 __global__ __launch_bounds__(64, 1) void ipm_kernel_dump(KernelArgs A, RestoDumpArgs Z)
 {
     Smem &S = instance_smem();
@@ -2833,13 +2772,15 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_dump(KernelArgs A, RestoDump
         typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
         KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         __asm__ volatile("" : "+s"(Ap));
-        run_instance<false, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, nullptr, nullptr, &Z);
+        run_instance<true, false>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, &Z);
     }
 }
 
-// The persistent solver with the pass of sens_ex.inc compiled in (lafse3_ocp_sensitivity_ex only): as ipm_kernel_sens
-// a further instantiation of run_instance in a kernel of its own with the plain queue-head loop.
-__global__ __launch_bounds__(64, 1) void ipm_kernel_sens_ex(KernelArgs A, SensExArgs Z)
+// The persistent solver with per-instance cost weights, the sensitivity pass of sens.inc and the optimum record compiled
+// in (lafse3_ocp_sensitivity / _ex / _w and lafse3_ocp_solve_rec): as ipm_kernel_dump a further instantiation of
+// run_instance in a kernel of its own with the plain queue-head loop.  One kernel serves the four entry points, so what
+// they share (the solve outputs, the columns of a group) is the same code and the same bits.
+__global__ __launch_bounds__(64, 1) void ipm_kernel_ext(KernelArgs A, ExtArgs Z)
 {
     Smem &S = instance_smem();
     gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
@@ -2851,44 +2792,7 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_sens_ex(KernelArgs A, SensEx
         typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
         KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         __asm__ volatile("" : "+s"(Ap));
-        run_instance<false, false, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, &Z);
-    }
-}
-
-// The persistent solver with per-instance cost weights and the pass of sens_w.inc compiled in
-// (lafse3_ocp_sensitivity_w only): as ipm_kernel_sens_ex a further instantiation of run_instance in a kernel of its own.
-__global__ __launch_bounds__(64, 1) void ipm_kernel_sens_w(KernelArgs A, SensWArgs Z)
-{
-    Smem &S = instance_smem();
-    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
-    for (;;) {
-        unsigned long long v = 0ull;
-        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
-        const int64_t inst = bcast_i64((int64_t)v);
-        if (inst >= A.n_inst) break;
-        typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
-        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-        __asm__ volatile("" : "+s"(Ap));
-        run_instance<false, false, false, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, nullptr, &Z);
-    }
-}
-
-// The persistent solver with per-instance cost weights that also stores the optimum record (lafse3_ocp_solve_rec only):
-// run_instance<.., SENSW, RECORD> in a kernel of its own with the plain queue-head loop and its own argument struct.
-__global__ __launch_bounds__(64, 1) void ipm_kernel_rec(KernelArgs A, RecArgs Z)
-{
-    Smem &S = instance_smem();
-    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
-    for (;;) {
-        unsigned long long v = 0ull;
-        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
-        const int64_t inst = bcast_i64((int64_t)v);
-        if (inst >= A.n_inst) break;
-        typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
-        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-        __asm__ volatile("" : "+s"(Ap));
-        run_instance<false, false, false, true, true>(*(const KernelArgs *)Ap, S, inst, ws, nullptr, nullptr, nullptr,
-                                                      nullptr, &Z);
+        run_instance<false, true>(*(const KernelArgs *)Ap, S, inst, ws, &Z);
     }
 }
 

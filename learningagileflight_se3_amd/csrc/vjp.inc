@@ -3,25 +3,25 @@
 //
 //   grad[q] = sum_k g_x[k] . dx*_k/dparam_q + sum_k g_u[k] . du*_k/dparam_q      for every selected column q
 //
-// The forward route (sens_w.inc) computes dz*/dparam_q = -K^{-1} c_q with one sweep per column.  K is symmetric, so
+// The forward route (sens.inc) computes dz*/dparam_q = -K^{-1} c_q with one sweep per column.  K is symmetric, so
 //   g^T (-K^{-1} c_q) = (-K^{-1} g)^T c_q = d . c_q,       d = the sweep on the right-hand side r = g,
-// which is sens_ex.inc's adjoint route with the unit vector e_(u_0, a) replaced by the incoming gradient: g_x of
+// which is sens.inc's adjoint route with the unit vector e_(u_0, a) replaced by the incoming gradient: g_x of
 // stages 1..N in the x rows (WS_RQ), g_u in the u rows (WS_RR), zero in the dynamics rows (WS_RC).  One factorisation
-// and one sweep per instance for any number of columns; the contraction is the gain block of sens_w_pass (x rows
-// against DX, u rows against DU, the ini_state group through At_times on lam+_0 plus the qu term).  Stage 0 is not a
-// decision variable: dx_0/dini_state is the identity, so g_x[0] is added to the ini_state columns directly.
+// and one sweep per instance for any number of columns; the contraction is sens_contract, the one sens_pass's gain
+// uses.  Stage 0 is not a decision variable: dx_0/dini_state is the identity, so g_x[0] is added to the ini_state
+// columns directly (sens_contract's gx0).
 //
-// The point comes from the record ipm_kernel_rec stored (REC_*), not from a solve on this wave: the instance prologue
+// The point comes from the record ipm_kernel_ext stored (REC_*), not from a solve on this wave: the instance prologue
 // of run_instance (Model and the weight row, attitude forms, S.wk, relaxed bounds, init_gv_const, goal / p_tra /
 // u_last) is repeated here from the same arguments, then x, u, the scaled lam, the bound duals, mu and the objective
-// scaling are loaded.  It is repeated, not shared: run_instance stays the code it is.
+// scaling are loaded.
 constexpr int VJP_HORIZON = 3;   // sens_status: the record's horizon is not the context's
 
 struct VjpArgs {
     lafse3_params prm;
     int64_t n_inst;
     const double *goal, *ptra, *atra, *t, *ulast;   // as KernelArgs (ini_state is stage 0 of the record's x)
-    const double *weights;                          // B x LAFSE3_NW or null, as SensWArgs
+    const double *weights;                          // B x LAFSE3_NW or null, as ExtArgs
     const double *rec;                              // B x REC_W
     const double *gx, *gu;                          // B x (N+1) x 13, B x N x 4 (each nullable: zero)
     double *grad;                                   // B x P
@@ -38,7 +38,7 @@ __device__ __attribute__((always_inline)) inline void vjp_instance(const VjpArgs
     const lafse3_params &prm = A.prm;
     const int N = prm.horizon;
     const int groups = A.groups;
-    const int P = sens_w_columns(groups);
+    const int P = sens_columns(groups);
     const double *rec = A.rec + inst * (int64_t)REC_W;
     double *o = A.grad + inst * (int64_t)P;
     // the scalars first: nothing is read by horizon from a record of another horizon
@@ -48,7 +48,7 @@ __device__ __attribute__((always_inline)) inline void vjp_instance(const VjpArgs
     st = __builtin_amdgcn_readfirstlane(st);   // every lane read the same words: uniform for the compiler too
 
     if (st == SENS_OK) {
-        // ---- instance prologue (run_instance, MODE_SOLVE with SENSW)
+        // ---- instance prologue (run_instance, MODE_SOLVE with EXT)
         Model &M = S.mdl;
         M = make_model(prm);
         double w_peak = prm.tra_w_peak, w_decay = prm.tra_w_decay;
@@ -133,7 +133,7 @@ __device__ __attribute__((always_inline)) inline void vjp_instance(const VjpArgs
         }
         vm_sync();
 
-        // ---- factorise at the recorded point, as sens_w_pass does
+        // ---- factorise at the recorded point, as sens_pass does
         int sw = 0;
         double rat[4];
         if (!linear_solve(M, S.at, S, C, ws, 0.0, 1, 0, 0, 0, sw, rat, nullptr)) st = SENS_INERTIA;
@@ -154,71 +154,11 @@ __device__ __attribute__((always_inline)) inline void vjp_instance(const VjpArgs
             vm_sync();
             linear_solve(M, S.at, S, C, ws, 0.0, 0, 0, 0, 0, sw, rat, nullptr);
             sync();
-            // ---- contraction with dF/dparam_q, column by column (the gain block of sens_w_pass)
+            // ---- contraction with dF/dparam_q, column by column
             // nothing per-lane is carried over from before the sweep (see above); the mask keeps the index's range
             // known, which the shared inline helpers' compares are specialised on in every kernel
             const int lane = opaque_lane() & (WAVE - 1);
-            lafse3_params pw;   // sens_column's t column reads dt and tra_w_decay: the instance's decay
-            pw.dt = prm.dt;
-            pw.tra_w_decay = w_decay;
-            int col = 0;
-            for (int grp = SENS_G_THETA; grp <= SENS_G_W; grp <<= 1) {
-                if (!(groups & grp)) continue;
-                if (grp == SENS_G_INI) {
-                    // stage 0 only: (A_0^T lam+_0)_i + qu_i (du_0[0] + .. + du_0[3]), plus g_x[0][i] for dx_0 = identity
-                    double x0[NX], u0[NU], l0[NX], lp0[NX], atl[NX];
-                    load_stage(S, 0, x0);
-                    load_u(S, 0, u0);
-#pragma unroll
-                    for (int i = 0; i < NX; ++i) {
-                        l0[i] = LAM[i * SX];
-                        lp0[i] = LP[i * SX];
-                    }
-                    At_times(M, x0, u0, lp0, atl);
-                    StageHess H;
-                    stage_hessian(M, S.at, C.s, 0.0, x0, u0, l0, H);
-                    double sdu = 0.0;
-#pragma unroll
-                    for (int b = 0; b < NU; ++b) sdu += DU[b * SX];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) atl[6 + i] += H.qu[i] * sdu;
-                    if (lane < NX) {
-                        double v = atl[0];
-#pragma unroll
-                        for (int i = 1; i < NX; ++i) v = (lane == i) ? atl[i] : v;
-                        o[col + lane] = v + (gx ? gx[lane] : 0.0);
-                    }
-                    col += NX;
-                    continue;
-                }
-                const int nq = sens_w_group_size(grp);
-                for (int q = 0; q < nq; ++q, ++col) {
-                    double acc = 0.0;
-                    if (grp == SENS_G_W) {
-                        if (lane <= N) {   // x rows k = 1..N against dx, u rows k = 0..N-1 against du
-                            const int k = lane;
-                            double vx[NX], vu[NU];
-                            sens_w_column(M, S, C, prm.dt, w_decay, tt, q, k, vx, vu);
-                            if (k >= 1) {
-#pragma unroll
-                                for (int i = 0; i < NX; ++i) acc = fma(DX[i * SX + k], vx[i], acc);
-                            }
-                            if (k < N) {
-#pragma unroll
-                                for (int b = 0; b < NU; ++b) acc = fma(DU[b * SX + k], vu[b], acc);
-                            }
-                        }
-                    } else if (lane >= 1 && lane <= N) {   // theta and goal columns have x rows only
-                        const int k = lane;
-                        double vx[NX], vu[NU], vc[NX];
-                        sens_column(pw, M, S, C, a3, tt, grp, q, k, vx, vu, vc);
-#pragma unroll
-                        for (int i = 0; i < NX; ++i) acc = fma(DX[i * SX + k], vx[i], acc);
-                    }
-                    acc = wsum(acc);
-                    if (lane == 0) o[col] = acc;
-                }
-            }
+            sens_contract(M, S, C, a3, prm.dt, w_decay, tt, groups, lane, gx, o);
         }
     }
     if (st != SENS_OK)
@@ -227,7 +167,7 @@ __device__ __attribute__((always_inline)) inline void vjp_instance(const VjpArgs
     sync();   // the next instance's prologue writes the LDS this one's last lanes may still read
 }
 
-// One wave per instance, the persistent queue-head loop and workspace slots of ipm_kernel_sens_w.
+// One wave per instance, the persistent queue-head loop and workspace slots of ipm_kernel_ext.
 __global__ __launch_bounds__(64, 1) void vjp_kernel(VjpArgs A)
 {
     Smem &S = instance_smem();

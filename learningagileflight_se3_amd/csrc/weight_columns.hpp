@@ -1,5 +1,5 @@
 // weight_columns.hpp — dF/dw of the KKT system for the ten cost weights, as closed forms on one lane's registers
-// (host + device: sens_w.inc uses them on the GPU, tests/native/weight_columns_host.cpp on the CPU).
+// (host + device: sens.inc uses them on the GPU, tests/native/weight_columns_host.cpp on the CPU).
 //
 // Column order = lafse3_params order (LAFSE3_NW):
 //   0 wrt  1 wqt  2 wthrust  3 wrf  4 wvf  5 wqf  6 wwf  7 tra_w_peak  8 tra_w_decay  9 du_weight

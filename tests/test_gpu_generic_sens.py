@@ -1,4 +1,4 @@
-"""lafse3_ocp_sensitivity_ex (csrc/sens.inc, csrc/sens_ex.inc) at the generic parameter set (generic_params.py): dt,
+"""lafse3_ocp_sensitivity_ex (csrc/sens.inc) at the generic parameter set (generic_params.py): dt,
 mass, arm_l, c_tau, grav, wthrust, du_weight, tra_w_peak and tra_w_decay enter the products dtm, bwx..bwz and dwk of the
 sensitivity right-hand sides, and an error that cancels at the reference's constants is invisible to
 test_gpu_sens.py / test_gpu_sens_ex.py.  Rules, constants and checking functions are those two files'.

@@ -1,4 +1,4 @@
-"""The weight columns of lafse3_ocp_sensitivity_w (csrc/sens_w.inc, csrc/weight_columns.hpp) and the adjoint sweep of
+"""The weight columns of lafse3_ocp_sensitivity_w (csrc/sens.inc, csrc/weight_columns.hpp) and the adjoint sweep of
 lafse3_ocp_vjp (csrc/vjp.inc) at the generic parameter set (generic_params.py).  tests/test_gpu_sens_w.py and
 tests/test_gpu_vjp.py take only the ten weights from that set: dt, the model and the bounds stay the reference's, a
 non-zero u_last appears at horizon 1 alone, and vjp.inc's hand-written copy of run_instance's prologue (relaxed bounds,

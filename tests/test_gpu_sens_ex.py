@@ -1,4 +1,4 @@
-"""GPU tests of lafse3_ocp_sensitivity_ex (csrc/sens_ex.inc): the sensitivities to ini_state and goal, the MPC
+"""GPU tests of lafse3_ocp_sensitivity_ex (csrc/sens.inc): the sensitivities to ini_state and goal, the MPC
 feedback gain from the adjoint use of the factorisation, and the autograd layers built on them (diff_mpc.mpc_layer
 with ini_state / goal leaves, diff_mpc.mpc_policy).
 

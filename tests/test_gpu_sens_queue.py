@@ -1,5 +1,5 @@
 """The sensitivity and adjoint kernels once a wave takes more than one instance: lafse3_ocp_sensitivity_ex,
-lafse3_ocp_sensitivity_w, lafse3_ocp_solve_rec (run_instance<.. SENSX / SENSW / RECORD> + sens_*_pass, rec_store) and
+lafse3_ocp_sensitivity_w, lafse3_ocp_solve_rec (ipm_kernel_ext: run_instance<.., EXT> + sens_pass, rec_store) and
 lafse3_ocp_vjp (vjp_instance).
 
 Run on an MI355X:  python -m pytest tests/test_gpu_sens_queue.py -m gpu -q -s

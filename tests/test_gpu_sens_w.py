@@ -1,4 +1,4 @@
-"""GPU tests of lafse3_ocp_sensitivity_w (csrc/sens_w.inc): per-instance cost weights, the sensitivities of the optimum
+"""GPU tests of lafse3_ocp_sensitivity_w (csrc/sens.inc): per-instance cost weights, the sensitivities of the optimum
 to the ten weights, and the autograd layers' ``weights=`` (diff_mpc.mpc_layer, diff_mpc.mpc_policy).
 
 Run on an MI355X:  python -m pytest tests/test_gpu_sens_w.py -m gpu -q -s

@@ -3,7 +3,7 @@ function by function: python tools/listing_diff.py parent.s new.s
 
 A function's body is the lines between its `name:` label and its `.Lfunc_end`, with comments, debug directives and
 blank lines dropped and the function's ordinal taken out of its local labels (.LBB<ordinal>_<n>), which shifts when
-a function is added in front.  Prints the functions whose bodies differ, those only one side has, and the count of
+a function is added in front, as does the module-wide counter of the long-branch labels (.Lpost_getpc<n>).  Prints the functions whose bodies differ, those only one side has, and the count of
 identical ones; exit status 1 when a function both sides have differs."""
 import re
 import sys
@@ -25,7 +25,7 @@ def functions(path):
         line = line.split(";", 1)[0].rstrip()
         if not line.strip() or re.match(r"\s*\.(loc|file|cfi_|p2align|section|type|size|globl|protected|weak)\b", line):
             continue
-        body.append(re.sub(r"\.L(BB|tmp|JTI|func_begin|func_end)\d+", r".L\1", line))
+        body.append(re.sub(r"\.L(BB|tmp|JTI|func_begin|func_end|post_getpc)\d+", r".L\1", line))
     return out
 
 
