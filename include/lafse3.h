@@ -253,6 +253,55 @@ int lafse3_ocp_vjp(lafse3_ctx *ctx, int64_t B, const double *ini_state, const do
                    const double *weights, const double *rec, const double *g_x, const double *g_u,
                    int32_t groups, double *grad, int32_t *sens_status, void *stream);
 
+/* Warm start from a saved optimum: lafse3_ocp_solve_rec whose instances start from the record of an earlier solve of the
+ * same or of a neighbouring problem (the receding-horizon successor: `shift` stages later) instead of the cold initial
+ * point.  The first nine arguments and the outputs x .. iters are lafse3_ocp_solve_rec's.
+ *   rec_in       B x lafse3_rec_width() (device; required: NULL is LAFSE3_EINVAL), records as lafse3_ocp_solve_rec or
+ *                this call wrote them
+ *   opts         NULL: lafse3_default_warm_opts (shift 0, mu_init 1e-3, the three pushes 1e-3: IPOPT's warm_start_*
+ *                defaults).  A negative shift, a negative push or a non-finite field is LAFSE3_EINVAL before any
+ *                launch; a shift of N or more acts as N (every stage is the record's last); mu_init <= 0 stands for
+ *                the context's params.mu_init
+ *   warm_status  B (nullable): 0 the instance started from its record, 1 the record was unusable and it started cold
+ *   rec_out      B x lafse3_rec_width() (nullable), the record of this solve; may alias rec_in: an instance reads the
+ *                whole of its record before it writes, and touches no other instance's
+ * One instance, N = params.horizon:
+ *   A record is usable when word 2222 equals N, word 2221 (status) is 0 or 1, words 2219 (mu) and 2220 (s) are finite
+ *   and positive, and every entry read below is finite.  The test comes before anything of the instance is written.
+ *   After an unusable record the instance is lafse3_ocp_solve_rec's: the cold start, every output bit for bit.
+ *   Shift.  With j = k + shift: x_k (k = 1..N) and the omega duals of stage k are the record's stage min(j, N);
+ *   u_k, lam_k and the duals of u_k (k = 0..N-1) its stage min(j, N-1), so past the record's end the last stage
+ *   repeats.  x_0 = ini_state; the omega duals of stage 0 are 0 (the stage is fixed).
+ *   Primal push.  u and the omega rows of x_1..x_N are moved into the relaxed bounds [lo, hi] (params.bound_relax) by
+ *   the cold start's formula with opts' numbers in place of its 1e-2:
+ *     pl = min(bound_push max(1, |lo|), bound_frac (hi - lo)),  pu = min(bound_push max(1, |hi|), bound_frac (hi - lo)),
+ *     v = min(max(v, lo + pl), hi - pu);
+ *   the other state rows are copied bit for bit.
+ *   Objective scaling.  s_new = min(1, 100 / max |dJ/d(x, u)|) at the loaded point (floor 1e-8), the rule of every
+ *   solve.  The record's multipliers are those of the problem whose objective is scaled by s_rec (word 2220), so
+ *     lam = lam_rec (s_new / s_rec),   z = max(z_rec (s_new / s_rec), mult_bound_push)  for the four bound-dual arrays.
+ *   Start.  No least-squares multiplier estimate (IPOPT with warm_start_init_point); mu = opts->mu_init.  The
+ *   iterations, the restoration phase, the watchdog and the final clamp are lafse3_ocp_solve's from there; the monotone
+ *   update lowers mu further at iteration 0 when the point is better than mu says.  With params.max_iter == 0 the
+ *   outputs and rec_out are the loaded point (status 2 unless it passes the convergence test).
+ * The problem is nonconvex: a warm start may end in another local optimum than the cold solve of the same arguments.  A
+ * warm start that fails (status > 1) is not retried here; the caller re-solves those instances with
+ * lafse3_ocp_solve_rec (Engine.ocp_solve_warm does).  rec_out is a valid `rec` of lafse3_ocp_vjp.  A solver launch for
+ * lafse3_reserve, lafse3_last_kernel_ms, the counters and lafse3_check_device; it runs on the caller's stream, allocates
+ * nothing once reserved, and leaves the caller's current device alone. */
+typedef struct lafse3_warm_opts {
+    int32_t shift;            /* stages the record is advanced by, 0 .. LAFSE3_MAX_N (more acts as the horizon) */
+    double  mu_init;          /* barrier parameter the warm solve starts with; <= 0: the context's params.mu_init */
+    double  bound_push, bound_frac;   /* IPOPT warm_start_bound_push / _frac */
+    double  mult_bound_push;          /* IPOPT warm_start_mult_bound_push */
+} lafse3_warm_opts;
+int lafse3_default_warm_opts(lafse3_warm_opts *o);
+int lafse3_ocp_solve_warm(lafse3_ctx *ctx, int64_t B, const double *ini_state, const double *goal,
+                          const double *p_tra, const double *a_tra, const double *t, const double *u_last,
+                          const double *weights, const double *rec_in, const lafse3_warm_opts *opts,
+                          double *x, double *u, double *lam, double *cost, int32_t *status, int32_t *iters,
+                          int32_t *warm_status, double *rec_out, void *stream);
+
 /* fp32 twin of lafse3_ocp_solve: the same arguments as float32 device buffers.  Inputs are
  * widened to fp64 and outputs rounded to fp32 on the device; the NLP itself is solved in fp64 (IPOPT's
  * 1e-8 tolerance, quad_OC.py:172, is below float32 resolution). */

@@ -54,6 +54,12 @@ class Params(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class WarmOpts(ctypes.Structure):
+    """Mirror of ``lafse3_warm_opts`` (include/lafse3.h)."""
+    _fields_ = [("shift", ctypes.c_int32), ("mu_init", ctypes.c_double), ("bound_push", ctypes.c_double),
+                ("bound_frac", ctypes.c_double), ("mult_bound_push", ctypes.c_double)]
+
+
 # exported symbol -> (restype, argtypes)
 _P = ctypes.POINTER
 _vp, _d, _i32, _i64 = ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int64
@@ -77,6 +83,9 @@ SIGNATURES = {
     "lafse3_ocp_sensitivity_w": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] + [_vp] * 6 + [_i32] + [_vp] * 4 + [_vp]),
     "lafse3_rec_width": (ctypes.c_int, []),
     "lafse3_ocp_solve_rec": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] + [_vp] * 6 + [_vp] + [_vp]),
+    "lafse3_default_warm_opts": (ctypes.c_int, [_P(WarmOpts)]),
+    "lafse3_ocp_solve_warm": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] + [_vp, _P(WarmOpts)] + [_vp] * 6
+                              + [_vp, _vp] + [_vp]),
     "lafse3_ocp_vjp": (ctypes.c_int, [_vp, _i64] + [_vp] * 6 + [_vp] + [_vp] * 3 + [_i32] + [_vp] * 2 + [_vp]),
     "lafse3_objective": (ctypes.c_int, [_vp, _i64] + [_vp] * 7 + [_vp, _vp, _vp]),
     "lafse3_sol_gradient": (ctypes.c_int, [_vp, _i64] + [_vp] * 5 + [_vp, _vp, _vp, _vp]),
@@ -127,6 +136,16 @@ def check(rc: int, what: str):
     if rc != 0:
         msg = load().lafse3_last_error().decode(errors="replace")
         raise Lafse3Error(f"{what} failed (rc={rc}): {msg}")
+
+
+def default_warm_opts(**overrides) -> WarmOpts:
+    o = WarmOpts()
+    check(load().lafse3_default_warm_opts(ctypes.byref(o)), "lafse3_default_warm_opts")
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise KeyError(k)
+        setattr(o, k, v)
+    return o
 
 
 def default_params(**overrides) -> Params:

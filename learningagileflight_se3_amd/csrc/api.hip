@@ -3,6 +3,7 @@
 // Host side only: argument checking, workspace management, kernel launches on the caller's stream.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
@@ -332,7 +333,7 @@ __global__ void slots_init_kernel(double *R, int32_t *S, int64_t n)
 }
 
 static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t sched_samples = 0,
-                  const lafse3::ExtArgs *ext = nullptr)
+                  const lafse3::ExtArgs *ext = nullptr, const lafse3::WarmArgs *warm = nullptr)
 {
     if (A.n_inst == 0) return LAFSE3_OK;
     // trajectory scoring (MODE_REWARD) counts nothing and has its own queue head: it leaves the last solver
@@ -388,8 +389,10 @@ static int launch(lafse3_ctx *c, lafse3::KernelArgs &A, hipStream_t st, int64_t 
     (void)hipEventRecord(c->ev0, st);
     // per-instance weights, the sensitivity pass and the optimum record are compiled into a kernel of their own
     // (ipm_kernel.hip ipm_kernel_ext), and so are the extra stores of a debug dump that carries the iterate
-    // (ipm_kernel_dump: plain solves only)
-    if (ext) hipLaunchKernelGGL(lafse3::ipm_kernel_ext, dim3((unsigned)grid), dim3(64), 0, st, A, *ext);
+    // (ipm_kernel_dump: plain solves only); the warm start has ipm_kernel_ext's arguments and its own (ipm_kernel_warm)
+    if (ext && warm)
+        hipLaunchKernelGGL(lafse3::ipm_kernel_warm, dim3((unsigned)grid), dim3(64), 0, st, A, *ext, *warm);
+    else if (ext) hipLaunchKernelGGL(lafse3::ipm_kernel_ext, dim3((unsigned)grid), dim3(64), 0, st, A, *ext);
     else if ((A.dump || c->rdump.buf) && A.mode == lafse3::MODE_SOLVE && !A.sched)
         hipLaunchKernelGGL(lafse3::ipm_kernel_dump, dim3((unsigned)grid), dim3(64), 0, st, A, c->rdump);
     else hipLaunchKernelGGL(lafse3::ipm_kernel, dim3((unsigned)grid), dim3(64), 0, st, A);
@@ -411,7 +414,8 @@ static lafse3::KernelArgs blank_args()
 // MODE_SOLVE arguments
 static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
                  const double *a_tra, const double *t, const double *u_last, double *x, double *u, double *lam,
-                 double *cost, int32_t *status, int32_t *iters, void *stream, const lafse3::ExtArgs *ext)
+                 double *cost, int32_t *status, int32_t *iters, void *stream, const lafse3::ExtArgs *ext,
+                 const lafse3::WarmArgs *warm = nullptr)
 {
     if (const int rc = check_call(c, B, {ini, goal, p_tra, a_tra, t})) return rc;
     if (B == 0) return LAFSE3_OK;
@@ -422,7 +426,7 @@ static int solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal
     A.n_inst = B;
     A.ini = ini; A.goal = goal; A.ptra = p_tra; A.atra = a_tra; A.t = t; A.ulast = u_last;
     A.x_out = x; A.u_out = u; A.lam_out = lam; A.cost_out = cost; A.status_out = status; A.iters_out = iters;
-    return launch(c, A, (hipStream_t)stream, 0, ext);
+    return launch(c, A, (hipStream_t)stream, 0, ext, warm);
 }
 
 int lafse3_ocp_solve(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
@@ -525,6 +529,45 @@ int lafse3_ocp_solve_rec(lafse3_ctx *c, int64_t B, const double *ini, const doub
     Z.weights = weights;
     Z.rec = rec;
     return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, &Z);
+}
+
+int lafse3_default_warm_opts(lafse3_warm_opts *o)
+{
+    if (!o) return fail(LAFSE3_EINVAL, "null warm opts");
+    std::memset(o, 0, sizeof(*o));
+    o->shift = 0;
+    o->mu_init = 1e-3;
+    o->bound_push = 1e-3; o->bound_frac = 1e-3; o->mult_bound_push = 1e-3;   // IPOPT warm_start_* defaults
+    return LAFSE3_OK;
+}
+
+int lafse3_ocp_solve_warm(lafse3_ctx *c, int64_t B, const double *ini, const double *goal, const double *p_tra,
+                          const double *a_tra, const double *t, const double *u_last, const double *weights,
+                          const double *rec_in, const lafse3_warm_opts *opts, double *x, double *u, double *lam,
+                          double *cost, int32_t *status, int32_t *iters, int32_t *warm_status, double *rec_out,
+                          void *stream)
+{
+    if (!c) return fail(LAFSE3_EINVAL, "bad ctx / batch");
+    if (!rec_in) return fail(LAFSE3_EINVAL, "lafse3_ocp_solve_warm: rec_in is required");
+    lafse3_warm_opts o;
+    lafse3_default_warm_opts(&o);
+    if (opts) o = *opts;
+    if (o.shift < 0) return fail(LAFSE3_EINVAL, "lafse3_ocp_solve_warm: negative shift");
+    if (!std::isfinite(o.mu_init) || !std::isfinite(o.bound_push) || !std::isfinite(o.bound_frac) ||
+        !std::isfinite(o.mult_bound_push))
+        return fail(LAFSE3_EINVAL, "lafse3_ocp_solve_warm: non-finite option");
+    if (o.bound_push < 0 || o.bound_frac < 0 || o.mult_bound_push < 0)
+        return fail(LAFSE3_EINVAL, "lafse3_ocp_solve_warm: negative push");
+    lafse3::ExtArgs Z = {};
+    Z.weights = weights;
+    Z.rec = rec_out;
+    lafse3::WarmArgs W = {};
+    W.rec_in = rec_in;
+    W.warm_out = warm_status;
+    W.shift = o.shift < LAFSE3_MAX_N ? o.shift : LAFSE3_MAX_N;   // past the horizon every stage is the record's last
+    W.mu_init = o.mu_init > 0 ? o.mu_init : c->prm.mu_init;
+    W.bound_push = o.bound_push; W.bound_frac = o.bound_frac; W.mult_bound_push = o.mult_bound_push;
+    return solve(c, B, ini, goal, p_tra, a_tra, t, u_last, x, u, lam, cost, status, iters, stream, &Z, &W);
 }
 
 // Not a solver launch (as trajectory scoring in launch()): its queue head is word 3 of the scoring counter block, and

@@ -1875,6 +1875,7 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 }
 
 #include "sens.inc"
+#include "warm.inc"
 
 // ------------------------------------------------------------------------------------------------
 // waves per SIMD the register allocation targets (LDS admits 2: Smem <= 20 KB)
@@ -1884,10 +1885,14 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 // EXT (ipm_kernel_ext): the instance's ten cost weights come from ZE->weights (MODE_SOLVE only), the pass of sens.inc
 // follows a MODE_SOLVE instance when dx, du or gain is asked for, and the optimum record is stored after the ordinary
 // outputs when ZE->rec is set (rec_store); ipm_kernel compiles none of it.
-template <bool DUMP, bool EXT>
+// WARM (ipm_kernel_warm, with EXT): an instance whose record ZW->rec_in is usable starts from it (warm.inc) instead of
+// the cold fill, without the least-squares multipliers and with mu = ZW->mu_init; the other kernels compile none of it
+// (`warm` is a constant false there).
+template <bool DUMP, bool EXT, bool WARM = false>
 __device__ __attribute__((always_inline)) inline int run_instance(const KernelArgs &A, Smem &S, const int64_t inst,
                                                                  gdouble *ws, const ExtArgs *ZE = nullptr,
-                                                                 const RestoDumpArgs *ZR = nullptr)
+                                                                 const RestoDumpArgs *ZR = nullptr,
+                                                                 const WarmArgs *ZW = nullptr)
 {
     const int lane = lane_id();
     const lafse3_params &prm = A.prm;
@@ -1992,6 +1997,15 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
     C.whi = prm.w_ub + prm.bound_relax * fmax(1.0, fabs(prm.w_ub));
     C.s = 1.0;
     C.mu = prm.mu_init;
+    // WARM: the vote on this instance's record, before anything of the instance is written
+    bool warm = false;
+    [[maybe_unused]] const gdouble *wrec = nullptr;
+    if constexpr (WARM) {
+        wrec = (const gdouble *)(ZW->rec_in + inst * (int64_t)REC_W);
+        warm = warm_usable(wrec, N, ZW->shift) != 0;
+        if (warm) C.mu = ZW->mu_init;
+        if (lane == 0 && ZW->warm_out) ZW->warm_out[inst] = warm ? 0 : 1;
+    }
 
     // ---- LDS init
 #ifdef LAFSE3_PHASE_TIMERS
@@ -2026,7 +2040,7 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
             at.trRg = Rg[0] + Rg[4] + Rg[8];
         }
     }
-    {
+    if (!warm) {
         const double umid = 0.5 * (prm.u_lb + prm.u_ub);
         const double wmid = 0.5 * (prm.w_lb + prm.w_ub);
         double pl = fmin(1e-2 * fmax(1.0, fabs(C.ulo)), 1e-2 * (C.uhi - C.ulo));
@@ -2070,6 +2084,10 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
             }
         }
     }
+    if constexpr (WARM)
+        if (warm)
+            warm_load_primal(S, wrec, A.ini + b * NX, ZW->shift, ZW->bound_push, ZW->bound_frac, prm.dt, tt, w_peak,
+                             w_decay);
     init_gv_const(M, S);
     vm_sync();
     // ---- gradient-based objective scaling
@@ -2089,8 +2107,13 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
         if (gm > 100.0) C.s = fmax(100.0 / gm, 1e-8);
     }
     int iters = 0, sweeps = 0, trials = 0;
-    // ---- least-squares constraint multipliers
-    if (prm.lsq_mult_init) {
+    if constexpr (WARM)
+        if (warm) {   // the record's multipliers, brought to this point's objective scaling
+            warm_load_duals(S, ws, wrec, ZW->shift, C.s / wrec[REC_S], ZW->mult_bound_push);
+            vm_sync();
+        }
+    // ---- least-squares constraint multipliers (a warm start keeps the record's, as IPOPT's warm_start_init_point)
+    if (prm.lsq_mult_init && !warm) {
         double rat[4];
         int ok = linear_solve(M, at, S, C, ws, 0.0, 1, 1, 0, 0, sweeps, rat, nullptr);
         if (ok) {
@@ -2793,6 +2816,25 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_ext(KernelArgs A, ExtArgs Z)
         KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
         __asm__ volatile("" : "+s"(Ap));
         run_instance<false, true>(*(const KernelArgs *)Ap, S, inst, ws, &Z);
+    }
+}
+
+// The persistent solver of lafse3_ocp_solve_warm: ipm_kernel_ext's instantiation (per-instance weights, the optimum
+// record) with the warm start of warm.inc compiled in, in a kernel of its own with the plain queue-head loop, so that
+// the other kernels' code is what it is without it.
+__global__ __launch_bounds__(64, 1) void ipm_kernel_warm(KernelArgs A, ExtArgs Z, WarmArgs W)
+{
+    Smem &S = instance_smem();
+    gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
+    for (;;) {
+        unsigned long long v = 0ull;
+        if (lane_id() == 0) v = atomicAdd(&A.counters[3], 1ull);
+        const int64_t inst = bcast_i64((int64_t)v);
+        if (inst >= A.n_inst) break;
+        typedef const KernelArgs __attribute__((address_space(4))) *KArgPtr;   // as in ipm_kernel
+        KArgPtr Ap = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+        __asm__ volatile("" : "+s"(Ap));
+        run_instance<false, true, true>(*(const KernelArgs *)Ap, S, inst, ws, &Z, nullptr, &W);
     }
 }
 

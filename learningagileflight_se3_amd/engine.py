@@ -13,6 +13,7 @@ Reference interfaces mirrored (yanrui89/LearningAgileFlight_SE3):
   Engine.ocp_sensitivity_ex  the same with ini_state and goal columns and the MPC feedback gain du*_0/dx_0
   Engine.ocp_sensitivity_w   the same with per-instance cost weights and the columns of the ten weights
   Engine.ocp_solve_rec / ocp_vjp   the solve that saves its optimum, and a loss's gradients from it in one adjoint sweep
+  Engine.ocp_solve_warm  the solve started from a saved optimum (same problem, or the receding-horizon successor)
 """
 from __future__ import annotations
 
@@ -442,6 +443,68 @@ class Engine:
                                            _ptr(w), _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]),
                                            _ptr(out["cost"]), _ptr(out["status"]), _ptr(out["iters"]),
                                            _ptr(out["rec"]), self._stream()), "lafse3_ocp_solve_rec")
+        return {k: v for k, v in out.items() if v is not None}
+
+    def ocp_solve_warm(self, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None, rec=None, shift=0,
+                       mu_init=None, retry=True, want=("x", "u", "lam", "cost"), opts=None, counters=None):
+        """ocp_solve_rec started from saved optima (lafse3_ocp_solve_warm): instance b starts from the record
+        ``rec[b]`` of an earlier solve, advanced by ``shift`` stages (the receding-horizon successor: shift=1 with
+        ini_state = the old x_1), instead of the cold initial point.
+
+        ``rec`` (B, rec_width()): records of ocp_solve_rec or of this call; it is not modified.  ``mu_init``: the
+        barrier parameter of a warm start (None: the default of lafse3_default_warm_opts, 1e-3; <= 0: the context's
+        params.mu_init).  ``opts``: a _lib.WarmOpts for the pushes as well; ``shift`` and ``mu_init`` override its
+        fields.  Returns ocp_solve_rec's dict (x, u, lam, cost as named in ``want``; status, iters, rec) plus
+          warm_status (B,) int32: 0 warm start, 1 the record was unusable (wrong horizon, status > 1, a non-finite
+          entry, mu or s not positive) and the instance started cold, bit for bit ocp_solve_rec's,
+          2 the warm start ended with status > 1 and the instance was solved again cold (``retry``).
+        ``retry=True``: the instances whose warm start failed are counted on the device (one host read), and when
+        there are any they are gathered, solved with ocp_solve_rec in a second launch and scattered back: every
+        output of such a row, its record included, is ocp_solve_rec's bit for bit, and ``iters`` is the retry's.
+        After a retry last_counters / last_kernel_ms describe the second launch; ``counters``, a list, receives
+        last_counters() + last_resto_counters() + kernel_ms after each launch made (diagnostics: each read waits for
+        its launch).  The returned ``rec`` is a valid input of ``ocp_vjp`` (with these arguments) and of the next
+        ocp_solve_warm.  The problem is nonconvex: a warm start may end in another local optimum than the cold
+        solve.  float64 only."""
+        d, f64 = self.device, torch.float64
+        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
+        w = _weight_rows(weights, B, d)
+        N = self.horizon
+        if rec is None:
+            raise ValueError("rec is required")
+        rec = rec.detach().to(device=d, dtype=f64).contiguous()
+        if tuple(rec.shape) != (B, self.rec_width()):
+            raise ValueError(f"rec: expected ({B}, {self.rec_width()}), got {tuple(rec.shape)}")
+        o = _lib.default_warm_opts() if opts is None else opts
+        o = _lib.WarmOpts(o.shift, o.mu_init, o.bound_push, o.bound_frac, o.mult_bound_push)
+        o.shift = int(shift)
+        if mu_init is not None:
+            o.mu_init = float(mu_init)
+        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,)}
+        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
+        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
+        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
+        out["warm_status"] = torch.empty((B,), dtype=torch.int32, device=d)
+        out["rec"] = torch.zeros((B, self.rec_width()), dtype=f64, device=d)
+        check(self._L.lafse3_ocp_solve_warm(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
+                                            _ptr(w), _ptr(rec), ctypes.byref(o), _ptr(out["x"]), _ptr(out["u"]),
+                                            _ptr(out["lam"]), _ptr(out["cost"]), _ptr(out["status"]),
+                                            _ptr(out["iters"]), _ptr(out["warm_status"]), _ptr(out["rec"]),
+                                            self._stream()), "lafse3_ocp_solve_warm")
+        if counters is not None:
+            counters.append(dict(self.last_counters(), **self.last_resto_counters(), kernel_ms=self.last_kernel_ms()))
+        if retry:
+            failed = (out["status"] > 1) & (out["warm_status"] == 0)
+            if int(failed.sum()) > 0:   # the one device-side count; the second launch only when it is non-zero
+                idx = failed.nonzero().squeeze(1)
+                cold = self.ocp_solve_rec(ini[idx], goal[idx], p[idx], a[idx], tt[idx],
+                                          None if ul is None else ul[idx], None if w is None else w[idx], want=want)
+                if counters is not None:
+                    counters.append(dict(self.last_counters(), **self.last_resto_counters(),
+                                         kernel_ms=self.last_kernel_ms()))
+                for k, v in cold.items():
+                    out[k][idx] = v
+                out["warm_status"][idx] = 2
         return {k: v for k, v in out.items() if v is not None}
 
     def ocp_vjp(self, ini_state, goal, p_tra, a_tra, t, u_last, weights, rec, g_x=None, g_u=None,

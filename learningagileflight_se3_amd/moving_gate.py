@@ -397,14 +397,52 @@ def plant_step_t(state, u, dt=DT_PLANT):
     return state + dt * f
 
 
+_REC_X_ROWS = (51, 13)   # the record's x block: LAFSE3_MAX_N + 1 rows of 13 (include/lafse3.h)
+
+
+def reframe_record_t(rec, IG_old, cen_old, IG_new, cen_new):
+    """Optimum records (B, rec_width) whose states are expressed in the gate frame (IG_old, cen_old) re-expressed in
+    the frame (IG_new, cen_new): with ``transform``'s maps p_G = IG (p - cen), v_G = IG v,
+        p_new = R p_old + IG_new (cen_old - cen_new),  v_new = R v_old,  R = IG_new IG_old^T,
+    applied to words 0..5 of each of the record's 51 state rows (x block, words 0..662, stage-major).  Every other
+    word -- quaternions, omega, u, lam, the bound duals, mu, s, status, horizon -- is carried as it is: the attitude
+    is not re-expressed, so the result is a starting guess for a warm start, not an optimum of the new problem.
+    Returns a new tensor; with IG_old = IG_new the identity matrix and equal centroids it equals ``rec``."""
+    B = rec.shape[0]
+    nrow, nx = _REC_X_ROWS
+    out = rec.clone()
+    x = out[:, :nrow * nx].view(B, nrow, nx)
+    R = torch.matmul(IG_new, IG_old.transpose(1, 2))
+    d = torch.einsum("bij,bj->bi", IG_new, cen_old - cen_new)
+    pos = torch.einsum("bij,bkj->bki", R, x[:, :, 0:3]) + d[:, None, :]
+    vel = torch.einsum("bij,bkj->bki", R, x[:, :, 3:6])
+    x[:, :, 0:3] = pos
+    x[:, :, 3:6] = vel
+    return out
+
+
+def _merge_counters(rows):
+    """One counters entry from those of the launches of one control step (sums)."""
+    return {k: sum(r[k] for r in rows) for k in rows[0]}
+
+
 def run_episodes_device(engine, net, samples, noise, v=(1.0, 0.3, 0.4), w=math.pi / 2, steps=500, check=4,
-                        graphs=True, fixed_point="kernel", counters=None, capture=None):
+                        graphs=True, fixed_point="kernel", counters=None, capture=None, warm=False):
     """run_episodes with the episode state on the GPU (gate motion precomputed by ``move`` on the host).
     fixed_point: "kernel" = one lafse3_traversal_time launch per plant step (HIP, the whole fixed point of
     quad_moving.solver with DNN2 inside); "torch" = solve_t_t as batched torch ops, through FixedPointGraph
     when graphs=True.  counters: a list that receives engine.last_counters() + kernel_ms after every get_input (diagnostics;
     each read waits for the launch).  capture: a list that receives, per get_input, the MPC instance inputs
-    (gate-frame state, gate-frame goal, DNN2 output, u_last) and the statuses (diagnostics / fixtures)."""
+    (gate-frame state, gate-frame goal, DNN2 output, u_last) and the statuses (diagnostics / fixtures).
+    warm=True: the MPC problem of a control step is the previous one advanced by one stage (CTRL_EVERY * DT_PLANT is
+    the stage dt), so every control step after the first starts from the previous step's optimum record
+    (engine.ocp_solve_warm, shift=1, cold retry of failed warm starts) instead of the cold initial point; the first
+    is engine.ocp_solve_rec.  The record's positions and velocities are re-expressed from the previous gate frame
+    into the current one (reframe_record_t); the rest is carried as it is -- a guess, which the solve corrects.  The
+    solves take DNN2's output widened to float64 (get_input forms |a_tra| in float32), and a warm start may reach
+    another local optimum, so the trajectory is close to warm=False's, not equal.  ``counters`` entries sum the
+    launches of a step (warm launch + retry), ``capture`` entries also hold x, u, lam and warm_status.
+    warm=False (the default) is the loop above, call for call."""
     dev = engine.device
     gp0, state0 = initial_episodes(samples)
     gate_move, V = move(gp0, v, w, noise[:, :max(steps, 1)])
@@ -419,6 +457,7 @@ def run_episodes_device(engine, net, samples, noise, v=(1.0, 0.3, 0.4), w=math.p
     if fixed_point not in ("kernel", "torch"):
         raise ValueError("fixed_point is 'kernel' or 'torch'")
     fp = FixedPointGraph(net, B, w, dev, check) if (graphs and fixed_point == "torch") else None
+    rec, frame = None, None   # warm: the previous control step's optimum records and their gate frame
     for i in range(steps):
         gp = gm[:, i]
         if fixed_point == "kernel":
@@ -434,15 +473,35 @@ def run_episodes_device(engine, net, samples, noise, v=(1.0, 0.3, 0.4), w=math.p
             with torch.no_grad():
                 out = net(inp.float())
             u_prev = u
-            u, st = engine.get_input(inp[:, 0:13].contiguous(), inp[:, 13:16].contiguous(), out.contiguous(), u)
+            step_counters = None   # warm: the counters of this step's launches
+            if warm:
+                IG, cen = gate_frame_t(gn), centroid_t(gn)
+                o64 = out.double()
+                sargs = (inp[:, 0:13].contiguous(), inp[:, 13:16].contiguous(), o64[:, 0:3].contiguous(),
+                         o64[:, 3:6].contiguous(), o64[:, 6].contiguous(), u_prev)
+                if rec is None:
+                    res = engine.ocp_solve_rec(*sargs)
+                else:
+                    step_counters = [] if counters is not None else None
+                    res = engine.ocp_solve_warm(*sargs, rec=reframe_record_t(rec, frame[0], frame[1], IG, cen),
+                                                shift=1, counters=step_counters)
+                rec, frame = res["rec"], (IG, cen)
+                u, st = res["u"][:, 0].contiguous(), res["status"]
+            else:
+                u, st = engine.get_input(inp[:, 0:13].contiguous(), inp[:, 13:16].contiguous(), out.contiguous(), u)
             stats.append(st)
             if capture is not None:
                 capture.append({"ini": inp[:, 0:13].clone(), "goal": inp[:, 13:16].clone(), "dnn_out": out.clone(),
                                 "u_last": u_prev.clone(), "status": st.clone(), "step": i})
+                if warm:
+                    capture[-1].update(x=res["x"], u=res["u"], lam=res["lam"], warm_status=res.get("warm_status"))
             solves += B
             if counters is not None:
-                counters.append(dict(engine.last_counters(), **engine.last_resto_counters(),
-                                     kernel_ms=engine.last_kernel_ms()))
+                if step_counters:
+                    counters.append(_merge_counters(step_counters))
+                else:
+                    counters.append(dict(engine.last_counters(), **engine.last_resto_counters(),
+                                         kernel_ms=engine.last_kernel_ms()))
         state = plant_step_t(state, u)
         states.append(state)
     return {"states": torch.stack(states, 1), "t": torch.stack(ts, 1), "status": torch.stack(stats, 1),
