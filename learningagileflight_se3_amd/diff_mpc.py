@@ -30,6 +30,24 @@ from __future__ import annotations
 import torch
 
 
+def _contract(dx, du, sens_status, g_x, g_u):
+    """The trajectory contraction: g (B, P) with
+      g[b, q] = sum_ki dx[b, q, k, i] g_x[b, k, i] + sum_ka du[b, q, k, a] g_u[b, k, a]
+    (g_x, g_u None = zero), accumulated in the Jacobians' dtype; rows with sens_status != 0 are zero."""
+    g = torch.zeros(dx.shape[:2], dtype=dx.dtype, device=dx.device)
+    if g_x is not None:
+        g = g + torch.einsum("bqki,bki->bq", dx, g_x.to(dx.dtype))
+    if g_u is not None:
+        g = g + torch.einsum("bqka,bka->bq", du, g_u.to(du.dtype))
+    return torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
+
+
+def _contract_gain(gain, sens_status, g_u0):
+    """The gain contraction: g[b, q] = sum_a gain[b, a, q] g_u0[b, a]; rows with sens_status != 0 are zero."""
+    g = torch.einsum("baq,ba->bq", gain, g_u0.to(gain.dtype))
+    return torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
+
+
 def mpc_backward(dx, du, sens_status, g_x, g_u, dtypes=None):
     """Vector-Jacobian product of the MPC layer on plain tensors (any device).
 
@@ -38,16 +56,55 @@ def mpc_backward(dx, du, sens_status, g_x, g_u, dtypes=None):
     Returns (grad_p (B, 3), grad_a (B, 3), grad_t (B,)) with
       grad_theta[b, q] = sum_ki dx[b, q, k, i] g_x[b, k, i] + sum_ka du[b, q, k, a] g_u[b, k, a],
     cast to ``dtypes`` = (p, a, t dtypes) when given."""
-    g = torch.zeros(dx.shape[:2], dtype=dx.dtype, device=dx.device)
-    if g_x is not None:
-        g = g + torch.einsum("bqki,bki->bq", dx, g_x.to(dx.dtype))
-    if g_u is not None:
-        g = g + torch.einsum("bqka,bka->bq", du, g_u.to(du.dtype))
-    g = torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
+    g = _contract(dx, du, sens_status, g_x, g_u)
     gp, ga, gt = g[:, 0:3], g[:, 3:6], g[:, 6]
     if dtypes is not None:
         gp, ga, gt = gp.to(dtypes[0]), ga.to(dtypes[1]), gt.to(dtypes[2])
     return gp, ga, gt
+
+
+# The parameter groups of Engine.ocp_sensitivity_w in column order (Engine.ocp_sensitivity_ex has the first three,
+# Engine.ocp_sensitivity the first), each with its columns and the positions of its inputs among (ini_state, goal,
+# p_tra, a_tra, t, weights) and their column ranges inside the group.
+_GROUPS = (("theta", 7, ((2, 0, 3), (3, 3, 6), (4, 6, 7))), ("ini", 13, ((0, 0, 13),)), ("goal", 3, ((1, 0, 3),)),
+           ("weights", 10, ((5, 0, 10),)))
+
+
+def _needs(ctx):
+    """needs_input_grad of (ini_state, goal, p_tra, a_tra, t[, weights]) among a Function's inputs
+    (engine, ini_state, goal, p_tra, a_tra, t, u_last[, weights])."""
+    return ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
+
+
+def _needed_groups(needs):
+    """The groups with an input that needs a gradient."""
+    return tuple(name for name, _, members in _GROUPS if any(needs[i] for i, _, _ in members))
+
+
+def _meta(v):
+    return (v.dtype, v.shape, v.device) if isinstance(v, torch.Tensor) else None
+
+
+def _input_grads(ctx, g):
+    """g (B, P): the gradient w.r.t. the P columns of ``ctx.groups`` -> backward()'s return: the gradients of
+    (ini_state, goal, p_tra, a_tra, t[, weights]) in the dtype, shape and device recorded in ``ctx.metas``, None for
+    an input that is no tensor or needs none, and None for the engine and u_last."""
+    needs = _needs(ctx)
+    out = [None] * len(ctx.metas)
+    col = 0
+    for name, n, members in _GROUPS:
+        if name not in ctx.groups:
+            continue
+        for i, lo, hi in members:
+            if ctx.metas[i] is None or not needs[i]:
+                continue
+            dtype, shape, device = ctx.metas[i]
+            gi = g[:, col + lo:col + hi]
+            # an input of one row (a scalar t) was broadcast over the batch: sum its gradient back
+            gi = gi if gi.numel() == shape.numel() else gi.sum(0)
+            out[i] = gi.reshape(shape).to(device=device, dtype=dtype)
+        col += n
+    return (None, *out[:5], None, *out[5:])
 
 
 class MPCFunction(torch.autograd.Function):
@@ -61,185 +118,74 @@ class MPCFunction(torch.autograd.Function):
     def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last=None):
         out = engine.ocp_sensitivity(ini_state, goal, p_tra, a_tra, t, u_last, want=("x", "u", "dx", "du"))
         ctx.save_for_backward(out["dx"], out["du"], out["sens_status"])
-        ctx.theta = tuple((v.dtype, v.shape, v.device) if isinstance(v, torch.Tensor) else None
-                          for v in (p_tra, a_tra, t))
+        ctx.groups = ("theta",)
+        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t))
         ctx.mark_non_differentiable(out["status"])
         return out["x"], out["u"], out["status"]
 
     @staticmethod
     def backward(ctx, g_x, g_u, _g_status):
-        dx, du, sens_status = ctx.saved_tensors
-        grads = mpc_backward(dx, du, sens_status, g_x, g_u)
-        out = []
-        for g, meta, need in zip(grads, ctx.theta, ctx.needs_input_grad[3:6]):
-            if meta is None or not need:
-                out.append(None)
-                continue
-            dtype, shape, device = meta
-            # a t of one element was broadcast over the batch (Engine.ocp_solve does the same): sum its gradient back
-            g = g if g.numel() == shape.numel() else g.sum()
-            out.append(g.reshape(shape).to(device=device, dtype=dtype))
-        return (None, None, None, out[0], out[1], out[2], None)
+        return _input_grads(ctx, _contract(*ctx.saved_tensors, g_x, g_u))
 
 
-# The parameter groups of Engine.ocp_sensitivity_ex in column order, each with its columns and the positions of
-# its inputs among (ini_state, goal, p_tra, a_tra, t) and their column ranges inside the group.
-_GROUPS = (("theta", 7, ((2, 0, 3), (3, 3, 6), (4, 6, 7))), ("ini", 13, ((0, 0, 13),)), ("goal", 3, ((1, 0, 3),)))
-
-
-# ... and of Engine.ocp_sensitivity_w, whose inputs are (ini_state, goal, p_tra, a_tra, t, weights)
-_GROUPS_W = _GROUPS + (("weights", 10, ((5, 0, 10),)),)
-
-
-def _needed_groups(needs, table=_GROUPS):
-    """needs: needs_input_grad of (ini_state, goal, p_tra, a_tra, t[, weights]) -> the groups with an input that
-    needs one."""
-    return tuple(name for name, _, members in table if any(needs[i] for i, _, _ in members))
-
-
-def _meta(v):
-    return (v.dtype, v.shape, v.device) if isinstance(v, torch.Tensor) else None
-
-
-def _scatter_columns(g, groups, metas, needs, table=_GROUPS):
-    """g (B, P): the gradient w.r.t. the P columns of ``groups`` -> the gradients of (ini_state, goal, p_tra, a_tra,
-    t[, weights]) in their dtype, shape and device; None for an input that is no tensor or needs none."""
-    out = [None] * len(metas)
-    col = 0
-    for name, n, members in table:
-        if name not in groups:
-            continue
-        for i, lo, hi in members:
-            if metas[i] is None or not needs[i]:
-                continue
-            dtype, shape, device = metas[i]
-            gi = g[:, col + lo:col + hi]
-            # an input of one row (a scalar t) was broadcast over the batch: sum its gradient back
-            gi = gi if gi.numel() == shape.numel() else gi.sum(0)
-            out[i] = gi.reshape(shape).to(device=device, dtype=dtype)
-        col += n
+def _sensitivity_forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights, plain, sens):
+    """The forward pass of MPCFunctionEx and MPCPolicyFunction: one ``Engine.ocp_sensitivity_ex`` launch, or with
+    ``weights`` one ``Engine.ocp_sensitivity_w`` launch, that asks for only the parameter groups with an input that
+    needs a gradient, and for the outputs ``plain`` plus, when there is such a group, ``sens``, which are saved for
+    backward() with sens_status.  Returns the engine's dict."""
+    ctx.groups = _needed_groups(_needs(ctx))
+    ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t, weights))
+    want = plain + sens if ctx.groups else plain
+    if weights is None:
+        out = engine.ocp_sensitivity_ex(ini_state, goal, p_tra, a_tra, t, u_last, groups=ctx.groups or ("theta",),
+                                        want=want)
+    else:
+        out = engine.ocp_sensitivity_w(ini_state, goal, p_tra, a_tra, t, u_last, weights=weights,
+                                       groups=ctx.groups or ("weights",), want=want)
+    if ctx.groups:
+        ctx.save_for_backward(*(out[k] for k in sens), out["sens_status"])
+    ctx.mark_non_differentiable(out["status"])
     return out
 
 
 class MPCFunctionEx(torch.autograd.Function):
-    """MPCFunction with gradients to ini_state and goal as well: (engine, ini_state, goal, p_tra, a_tra, t, u_last)
-    -> (x, u, status).  One ``Engine.ocp_sensitivity_ex`` launch that asks for only the parameter groups with an
-    input that needs a gradient; each such input receives its gradient in its own dtype and shape.  u_last and the
-    engine get none.  The quaternion entries of ini_state are differentiated as the four raw numbers the solver
-    reads."""
+    """MPCFunction with gradients to ini_state and goal as well, and under per-instance cost weights:
+    (engine, ini_state, goal, p_tra, a_tra, t, u_last, weights) -> (x, u, status).  One launch
+    (_sensitivity_forward); each input that needs a gradient receives it in its own dtype and shape.  ``weights`` is
+    None (the context's weights), (B, 10) or (10,) (broadcast; its gradient is then summed over the batch).  u_last
+    and the engine get none.  The quaternion entries of ini_state are differentiated as the four raw numbers the
+    solver reads."""
 
     @staticmethod
-    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last=None):
-        needs = ctx.needs_input_grad[1:6]
-        ctx.groups = _needed_groups(needs)
-        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t))
-        want = ("x", "u", "dx", "du") if ctx.groups else ("x", "u")
-        out = engine.ocp_sensitivity_ex(ini_state, goal, p_tra, a_tra, t, u_last, groups=ctx.groups or ("theta",),
-                                        want=want)
-        if ctx.groups:
-            ctx.save_for_backward(out["dx"], out["du"], out["sens_status"])
-        ctx.mark_non_differentiable(out["status"])
+    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights):
+        out = _sensitivity_forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights,
+                                   plain=("x", "u"), sens=("dx", "du"))
         return out["x"], out["u"], out["status"]
 
     @staticmethod
     def backward(ctx, g_x, g_u, _g_status):
-        dx, du, sens_status = ctx.saved_tensors
-        g = torch.zeros(dx.shape[:2], dtype=dx.dtype, device=dx.device)
-        if g_x is not None:
-            g = g + torch.einsum("bqki,bki->bq", dx, g_x.to(dx.dtype))
-        if g_u is not None:
-            g = g + torch.einsum("bqka,bka->bq", du, g_u.to(du.dtype))
-        g = torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
-        return (None, *_scatter_columns(g, ctx.groups, ctx.metas, ctx.needs_input_grad[1:6]), None)
+        return _input_grads(ctx, _contract(*ctx.saved_tensors, g_x, g_u))
 
 
 class MPCPolicyFunction(torch.autograd.Function):
-    """(engine, ini_state, goal, p_tra, a_tra, t, u_last) -> (u0 (B, 4), status (B,)): the first control of the
-    optimum, differentiable in ini_state, goal, p_tra, a_tra and t through ``gain`` alone (four adjoint sweeps on the
-    factorisation at the optimum; no dx, no du).  Over ini_state the Jacobian is the MPC feedback gain."""
+    """(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights) -> (u0 (B, 4), status (B,)): the first control of
+    the optimum, differentiable in ini_state, goal, p_tra, a_tra, t and ``weights`` (as in MPCFunctionEx) through
+    ``gain`` alone (four adjoint sweeps on the factorisation at the optimum; no dx, no du).  Over ini_state the
+    Jacobian is the MPC feedback gain."""
 
     @staticmethod
-    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last=None):
-        needs = ctx.needs_input_grad[1:6]
-        ctx.groups = _needed_groups(needs)
-        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t))
-        out = engine.ocp_sensitivity_ex(ini_state, goal, p_tra, a_tra, t, u_last, groups=ctx.groups or ("theta",),
-                                        want=("u", "gain") if ctx.groups else ("u",))
-        if ctx.groups:
-            ctx.save_for_backward(out["gain"], out["sens_status"])
-        ctx.mark_non_differentiable(out["status"])
+    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights):
+        out = _sensitivity_forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights,
+                                   plain=("u",), sens=("gain",))
         return out["u"][:, 0].contiguous(), out["status"]
 
     @staticmethod
     def backward(ctx, g_u0, _g_status):
-        gain, sens_status = ctx.saved_tensors
-        g = torch.einsum("baq,ba->bq", gain, g_u0.to(gain.dtype))
-        g = torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
-        return (None, *_scatter_columns(g, ctx.groups, ctx.metas, ctx.needs_input_grad[1:6]), None)
-
-
-class MPCFunctionW(torch.autograd.Function):
-    """MPCFunctionEx under per-instance cost weights: (engine, ini_state, goal, p_tra, a_tra, t, u_last, weights) ->
-    (x, u, status).  One ``Engine.ocp_sensitivity_w`` launch; ``weights`` is (B, 10) or (10,) (broadcast; its gradient
-    is then summed over the batch) and, like the other five inputs, receives a gradient in its own dtype and shape
-    when it requires one."""
-
-    @staticmethod
-    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights):
-        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
-        ctx.groups = _needed_groups(needs, _GROUPS_W)
-        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t, weights))
-        want = ("x", "u", "dx", "du") if ctx.groups else ("x", "u")
-        out = engine.ocp_sensitivity_w(ini_state, goal, p_tra, a_tra, t, u_last, weights=weights,
-                                       groups=ctx.groups or ("weights",), want=want)
-        if ctx.groups:
-            ctx.save_for_backward(out["dx"], out["du"], out["sens_status"])
-        ctx.mark_non_differentiable(out["status"])
-        return out["x"], out["u"], out["status"]
-
-    @staticmethod
-    def backward(ctx, g_x, g_u, _g_status):
-        dx, du, sens_status = ctx.saved_tensors
-        g = torch.zeros(dx.shape[:2], dtype=dx.dtype, device=dx.device)
-        if g_x is not None:
-            g = g + torch.einsum("bqki,bki->bq", dx, g_x.to(dx.dtype))
-        if g_u is not None:
-            g = g + torch.einsum("bqka,bka->bq", du, g_u.to(du.dtype))
-        g = torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
-        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
-        gr = _scatter_columns(g, ctx.groups, ctx.metas, needs, _GROUPS_W)
-        return (None, *gr[:5], None, gr[5])
-
-
-class MPCPolicyFunctionW(torch.autograd.Function):
-    """MPCPolicyFunction under per-instance cost weights: (engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
-    -> (u0, status), differentiable in the five inputs and the weights through ``gain`` alone."""
-
-    @staticmethod
-    def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights):
-        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
-        ctx.groups = _needed_groups(needs, _GROUPS_W)
-        ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t, weights))
-        out = engine.ocp_sensitivity_w(ini_state, goal, p_tra, a_tra, t, u_last, weights=weights,
-                                       groups=ctx.groups or ("weights",),
-                                       want=("u", "gain") if ctx.groups else ("u",))
-        if ctx.groups:
-            ctx.save_for_backward(out["gain"], out["sens_status"])
-        ctx.mark_non_differentiable(out["status"])
-        return out["u"][:, 0].contiguous(), out["status"]
-
-    @staticmethod
-    def backward(ctx, g_u0, _g_status):
-        gain, sens_status = ctx.saved_tensors
-        g = torch.einsum("baq,ba->bq", gain, g_u0.to(gain.dtype))
-        g = torch.where((sens_status != 0).unsqueeze(1), torch.zeros_like(g), g)
-        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
-        gr = _scatter_columns(g, ctx.groups, ctx.metas, needs, _GROUPS_W)
-        return (None, *gr[:5], None, gr[5])
+        return _input_grads(ctx, _contract_gain(*ctx.saved_tensors, g_u0))
 
 
 class MPCFunctionAdj(torch.autograd.Function):
-    """The adjoint route of MPCFunctionW: (engine, ini_state, goal, p_tra, a_tra, t, u_last, weights) -> (x, u, status)
+    """The adjoint route of MPCFunctionEx: (engine, ini_state, goal, p_tra, a_tra, t, u_last, weights) -> (x, u, status)
     with the same gradients, computed at ``backward()`` time instead of stored at forward time.
 
     forward is one ``Engine.ocp_solve_rec`` launch; it saves the optimum record (``Engine.rec_width()`` doubles per
@@ -251,8 +197,7 @@ class MPCFunctionAdj(torch.autograd.Function):
     @staticmethod
     def forward(ctx, engine, ini_state, goal, p_tra, a_tra, t, u_last, weights):
         inputs = (ini_state, goal, p_tra, a_tra, t, u_last, weights)
-        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
-        ctx.groups = _needed_groups(needs, _GROUPS_W)
+        ctx.groups = _needed_groups(_needs(ctx))
         ctx.metas = tuple(_meta(v) for v in (ini_state, goal, p_tra, a_tra, t, weights))
         out = engine.ocp_solve_rec(ini_state, goal, p_tra, a_tra, t, u_last, weights=weights, want=("x", "u"))
         if ctx.groups:
@@ -270,10 +215,7 @@ class MPCFunctionAdj(torch.autograd.Function):
         rec, *saved = ctx.saved_tensors
         saved = iter(saved)
         inputs = [next(saved) if s else v for v, s in zip(ctx.plain, ctx.is_tensor)]
-        res = ctx.engine.ocp_vjp(*inputs, rec, g_x, g_u, groups=ctx.groups)
-        needs = ctx.needs_input_grad[1:6] + ctx.needs_input_grad[7:8]
-        gr = _scatter_columns(res["grad"], ctx.groups, ctx.metas, needs, _GROUPS_W)
-        return (None, *gr[:5], None, gr[5])
+        return _input_grads(ctx, ctx.engine.ocp_vjp(*inputs, rec, g_x, g_u, groups=ctx.groups)["grad"])
 
 
 def _wants_grad(v):
@@ -283,10 +225,10 @@ def _wants_grad(v):
 def mpc_layer(engine, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None, backward="jacobian"):
     """Differentiable batched MPC solve -> (x, u, status); see MPCFunction.  When ini_state or goal is a tensor that
     requires a gradient, the solve goes through MPCFunctionEx, which also returns gradients to them.  ``weights``
-    ((B, 10) or (10,), the cost weights of each instance): the solve goes through MPCFunctionW, and a ``weights`` that
-    requires a gradient receives one.
+    ((B, 10) or (10,), the cost weights of each instance): the solve goes through MPCFunctionEx under those weights
+    (Engine.ocp_sensitivity_w), and a ``weights`` that requires a gradient receives one.
 
-    ``backward``: "jacobian" (the default) is those three functions, which store dx*/dparam and du*/dparam of every
+    ``backward``: "jacobian" (the default) is those two functions, which store dx*/dparam and du*/dparam of every
     selected column at forward time (B x P x 863 doubles) and contract them in ``backward()``.  "adjoint" selects
     MPCFunctionAdj for any combination of inputs and weights: the forward launch saves the optimum itself (about 18 KB
     per instance for any P) and ``backward()`` runs one adjoint sweep per instance.  Same gradients up to rounding;
@@ -295,17 +237,13 @@ def mpc_layer(engine, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=Non
         return MPCFunctionAdj.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
     if backward != "jacobian":
         raise ValueError(f'backward: expected "jacobian" or "adjoint", got {backward!r}')
-    if weights is not None:
-        return MPCFunctionW.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
-    if _wants_grad(ini_state) or _wants_grad(goal):
-        return MPCFunctionEx.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last)
+    if weights is not None or _wants_grad(ini_state) or _wants_grad(goal):
+        return MPCFunctionEx.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
     return MPCFunction.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last)
 
 
 def mpc_policy(engine, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None):
     """The MPC policy u0 = u*_0(ini_state, goal, p_tra, a_tra, t) -> (u0 (B, 4), status), differentiable in all five
     (see MPCPolicyFunction): the layer for closed-loop rollouts x_{t+1} = plant(x_t, u0(x_t, ..)).  ``weights`` as in
-    mpc_layer (MPCPolicyFunctionW)."""
-    if weights is not None:
-        return MPCPolicyFunctionW.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)
-    return MPCPolicyFunction.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last)
+    mpc_layer."""
+    return MPCPolicyFunction.apply(engine, ini_state, goal, p_tra, a_tra, t, u_last, weights)

@@ -101,23 +101,22 @@ def _param_override(eng, field, value):
         eng.set_params(eng.params)
 
 
-def _groups_w(groups, required=True):
-    """``groups`` of the calls with the four parameter groups (names of _lib.SENS_GROUPS_W, one name, or the
-    LAFSE3_SENS_* bit mask) -> (mask, column names in the fixed order).  ``required``: an empty selection or a bit
-    outside the four groups raises ValueError."""
-    G = _lib.SENS_GROUPS_W
+def _parse_groups(groups, table, required=True):
+    """``groups`` (names of ``table``, one name, or the LAFSE3_SENS_* bit mask) -> (mask, column names in the fixed
+    order); ``table`` is _lib.SENS_GROUPS or, for the calls with the weights group, _lib.SENS_GROUPS_W.  ``required``:
+    an empty selection or a bit outside the table raises ValueError."""
     if isinstance(groups, str):
         groups = (groups,)
     if isinstance(groups, int):
         mask = int(groups)
     else:
-        unknown = [g for g in groups if g not in G]
+        unknown = [g for g in groups if g not in table]
         if unknown:
-            raise ValueError(f"groups: unknown {unknown}; expected any of {list(G)}")
-        mask = sum(bit for g, bit in G.items() if g in groups)
-    if required and (mask == 0 or mask & ~sum(G.values())):
-        raise ValueError(f"groups: {groups!r} selects no column or a bit outside {G}")
-    return mask, [c for g, bit in G.items() if mask & bit for c in _lib.SENS_COLUMNS_W[g]]
+            raise ValueError(f"groups: unknown {unknown}; expected any of {list(table)}")
+        mask = sum(bit for g, bit in table.items() if g in groups)
+    if required and (mask == 0 or mask & ~sum(table.values())):
+        raise ValueError(f"groups: {groups!r} selects no column or a bit outside {table}")
+    return mask, [c for g, bit in table.items() if mask & bit for c in _lib.SENS_COLUMNS_W[g]]
 
 
 def _weight_rows(weights, B, device):
@@ -137,6 +136,17 @@ def _weight_rows(weights, B, device):
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _solve_outputs(B, N, want, dtype, device, **extra):
+    """The outputs every solve entry point has, in the order the results are returned in: x, u, lam, cost and the
+    ``extra`` name=shape ones as uninitialised ``dtype`` tensors, None for one not in ``want``, then status and iters
+    (B,) int32."""
+    shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,), **extra}
+    out = {k: torch.empty(s, dtype=dtype, device=device) if k in want else None for k, s in shapes.items()}
+    out["status"] = torch.empty((B,), dtype=torch.int32, device=device)
+    out["iters"] = torch.empty((B,), dtype=torch.int32, device=device)
+    return out
 
 
 class QueueStream:
@@ -277,6 +287,29 @@ class Engine:
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ hot path
+    def _solve_call(self, entry, B, inputs, out, before=(), after=()):
+        """The one call into the solve entry points, whose C signatures share the skeleton
+          ctx, B, ini_state .. u_last, [before], x, u, lam, cost, status, iters, [after], stream.
+        ``inputs``: the six tensors of _solve_inputs; ``out``: _solve_outputs' dict plus the entry's own outputs;
+        ``before`` / ``after``: the entry's own arguments on either side of the common outputs, as ctypes takes them.
+        Raises Lafse3Error under the entry's name; returns ``out`` without its None entries."""
+        check(getattr(self._L, entry)(self._ctx, B, *map(_ptr, inputs), *before,
+                                      _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]), _ptr(out["cost"]),
+                                      _ptr(out["status"]), _ptr(out["iters"]), *after, self._stream()), entry)
+        return {k: v for k, v in out.items() if v is not None}
+
+    def _rec_rows(self, rec, B):
+        """``rec`` as a contiguous (B, rec_width()) float64 tensor on the engine's device; ValueError otherwise."""
+        if rec is None:
+            raise ValueError("rec is required")
+        rec = rec.detach().to(device=self.device, dtype=torch.float64).contiguous()
+        if tuple(rec.shape) != (B, self.rec_width()):
+            raise ValueError(f"rec: expected ({B}, {self.rec_width()}), got {tuple(rec.shape)}")
+        return rec
+
+    def _launch_counters(self) -> dict:
+        return dict(self.last_counters(), **self.last_resto_counters(), kernel_ms=self.last_kernel_ms())
+
     def ocp_solve(self, ini_state, goal, p_tra, a_tra, t, u_last=None, want=("x", "u", "lam", "cost"),
                   costate_option: int | None = None, dtype=torch.float64):
         """Batched OCSys.ocSolver. Returns dict of device tensors (x, u, lam, cost, status, iters).
@@ -286,24 +319,11 @@ class Engine:
         (lafse3_ocp_solve_f32: float32 buffers at the boundary, fp64 solve inside).
         """
         f32 = dtype == torch.float32
-        d, f64 = self.device, (torch.float32 if f32 else torch.float64)
-        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
-        N = self.horizon
-        out = {
-            "x": torch.empty((B, N + 1, NX), dtype=f64, device=d) if "x" in want else None,
-            "u": torch.empty((B, N, NU), dtype=f64, device=d) if "u" in want else None,
-            "lam": torch.empty((B, N, NX), dtype=f64, device=d) if "lam" in want else None,
-            "cost": torch.empty((B,), dtype=f64, device=d) if "cost" in want else None,
-            "status": torch.empty((B,), dtype=torch.int32, device=d),
-            "iters": torch.empty((B,), dtype=torch.int32, device=d),
-        }
-        fn = self._L.lafse3_ocp_solve_f32 if f32 else self._L.lafse3_ocp_solve
+        d, dt = self.device, (torch.float32 if f32 else torch.float64)
+        B, *inputs, _ = _solve_inputs(d, dt, ini_state, goal, p_tra, a_tra, t, u_last)
+        out = _solve_outputs(B, self.horizon, want, dt, d)
         with _param_override(self, "costate_option", costate_option):
-            check(fn(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
-                     _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]), _ptr(out["cost"]),
-                     _ptr(out["status"]), _ptr(out["iters"]), self._stream()),
-                  "lafse3_ocp_solve_f32" if f32 else "lafse3_ocp_solve")
-        return {k: v for k, v in out.items() if v is not None}
+            return self._solve_call("lafse3_ocp_solve_f32" if f32 else "lafse3_ocp_solve", B, inputs, out)
 
     def ocp_sensitivity(self, ini_state, goal, p_tra, a_tra, t, u_last=None, want=("x", "u", "dx", "du")):
         """ocp_solve plus the analytic sensitivities of its solution (lafse3_ocp_sensitivity), one launch.
@@ -315,20 +335,32 @@ class Engine:
           (dx and du of such an instance are zero).
         The derivative is that of the barrier problem at the final mu (include/lafse3.h).  float64 only."""
         d, f64 = self.device, torch.float64
-        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
+        B, *inputs, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
         N = self.horizon
-        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,),
-                  "dx": (B, 7, N + 1, NX), "du": (B, 7, N, NU)}
-        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
-        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
-        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
-        if out["dx"] is not None or out["du"] is not None:   # without either the call is lafse3_ocp_solve
-            out["sens_status"] = torch.empty((B,), dtype=torch.int32, device=d)
-        check(self._L.lafse3_ocp_sensitivity(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
-                                             _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]), _ptr(out["cost"]),
-                                             _ptr(out["status"]), _ptr(out["iters"]), _ptr(out["dx"]), _ptr(out["du"]),
-                                             _ptr(out.get("sens_status")), self._stream()), "lafse3_ocp_sensitivity")
-        return {k: v for k, v in out.items() if v is not None}
+        out = _solve_outputs(B, N, want, f64, d, dx=(B, 7, N + 1, NX), du=(B, 7, N, NU))
+        # without dx and du the call is lafse3_ocp_solve
+        out["sens_status"] = torch.empty((B,), dtype=torch.int32, device=d) if "dx" in want or "du" in want else None
+        return self._solve_call("lafse3_ocp_sensitivity", B, inputs, out,
+                                after=(_ptr(out["dx"]), _ptr(out["du"]), _ptr(out["sens_status"])))
+
+    def _sensitivity_groups(self, entry, table, args, weights, groups, want):
+        """ocp_sensitivity_ex and ocp_sensitivity_w, which differ in the entry point, the group table and the
+        ``weights`` argument (passed when the table has the weights group)."""
+        sens = any(k in want for k in ("dx", "du", "gain"))
+        mask, columns = _parse_groups(groups, table, required=sens)
+        P = len(columns)
+        d, f64 = self.device, torch.float64
+        B, *inputs, _ = _solve_inputs(d, f64, *args)
+        w = _weight_rows(weights, B, d)
+        N = self.horizon
+        out = _solve_outputs(B, N, want, f64, d, dx=(B, P, N + 1, NX), du=(B, P, N, NU), gain=(B, NU, P))
+        # without dx, du and gain the call is a plain solve
+        out["sens_status"] = torch.empty((B,), dtype=torch.int32, device=d) if sens else None
+        res = self._solve_call(entry, B, inputs, out, before=(_ptr(w),) if "weights" in table else (),
+                               after=(mask, _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["gain"]),
+                                      _ptr(out["sens_status"])))
+        res["columns"] = columns
+        return res
 
     def ocp_sensitivity_ex(self, ini_state, goal, p_tra, a_tra, t, u_last=None, groups=("theta", "ini", "goal"),
                            want=("x", "u", "dx", "du", "gain")):
@@ -342,39 +374,8 @@ class Engine:
           columns: the P column names in order ("p_tra[0]", .., "ini_state[0]", .., "goal[2]").
         dx and du cost one sweep per column, gain four sweeps in all; want=("gain",) computes nothing else.
         After sens_status != 0 an instance's dx, du and gain are zero.  float64 only."""
-        if isinstance(groups, str):
-            groups = (groups,)
-        if isinstance(groups, int):
-            mask = int(groups)
-        else:
-            unknown = [g for g in groups if g not in _lib.SENS_GROUPS]
-            if unknown:
-                raise ValueError(f"groups: unknown {unknown}; expected any of {list(_lib.SENS_GROUPS)}")
-            mask = sum(bit for g, bit in _lib.SENS_GROUPS.items() if g in groups)
-        sens = any(k in want for k in ("dx", "du", "gain"))
-        if sens and (mask == 0 or mask & ~sum(_lib.SENS_GROUPS.values())):
-            raise ValueError(f"groups: {groups!r} selects no column or a bit outside {_lib.SENS_GROUPS}")
-        columns = [c for g, bit in _lib.SENS_GROUPS.items() if mask & bit for c in _lib.SENS_COLUMNS[g]]
-        P = len(columns)
-        d, f64 = self.device, torch.float64
-        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
-        N = self.horizon
-        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,),
-                  "dx": (B, P, N + 1, NX), "du": (B, P, N, NU), "gain": (B, NU, P)}
-        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
-        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
-        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
-        if any(out[k] is not None for k in ("dx", "du", "gain")):   # without any the call is lafse3_ocp_solve
-            out["sens_status"] = torch.empty((B,), dtype=torch.int32, device=d)
-        check(self._L.lafse3_ocp_sensitivity_ex(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt),
-                                                _ptr(ul), _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]),
-                                                _ptr(out["cost"]), _ptr(out["status"]), _ptr(out["iters"]), mask,
-                                                _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["gain"]),
-                                                _ptr(out.get("sens_status")), self._stream()),
-              "lafse3_ocp_sensitivity_ex")
-        res = {k: v for k, v in out.items() if v is not None}
-        res["columns"] = columns
-        return res
+        return self._sensitivity_groups("lafse3_ocp_sensitivity_ex", _lib.SENS_GROUPS,
+                                        (ini_state, goal, p_tra, a_tra, t, u_last), None, groups, want)
 
     def weights(self):
         """The context's ten cost weights (_lib.WEIGHT_NAMES order) as a (10,) float64 device tensor: the row a
@@ -394,29 +395,8 @@ class Engine:
         ``groups``: as ocp_sensitivity_ex plus "weights" (10 columns, last).  Returns ocp_sensitivity_ex's dict;
         ``columns`` ends with the ten weight names.  Without dx, du and gain in ``want`` the call is a plain solve
         with those weights.  float64 only."""
-        sens = any(k in want for k in ("dx", "du", "gain"))
-        mask, columns = _groups_w(groups, required=sens)
-        P = len(columns)
-        d, f64 = self.device, torch.float64
-        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
-        w = _weight_rows(weights, B, d)
-        N = self.horizon
-        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,),
-                  "dx": (B, P, N + 1, NX), "du": (B, P, N, NU), "gain": (B, NU, P)}
-        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
-        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
-        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
-        if sens:   # without dx, du and gain the call is a plain solve
-            out["sens_status"] = torch.empty((B,), dtype=torch.int32, device=d)
-        check(self._L.lafse3_ocp_sensitivity_w(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt),
-                                               _ptr(ul), _ptr(w), _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]),
-                                               _ptr(out["cost"]), _ptr(out["status"]), _ptr(out["iters"]), mask,
-                                               _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["gain"]),
-                                               _ptr(out.get("sens_status")), self._stream()),
-              "lafse3_ocp_sensitivity_w")
-        res = {k: v for k, v in out.items() if v is not None}
-        res["columns"] = columns
-        return res
+        return self._sensitivity_groups("lafse3_ocp_sensitivity_w", _lib.SENS_GROUPS_W,
+                                        (ini_state, goal, p_tra, a_tra, t, u_last), weights, groups, want)
 
     def rec_width(self) -> int:
         """Doubles per instance of the optimum record (lafse3_rec_width; independent of the horizon)."""
@@ -430,20 +410,12 @@ class Engine:
           rec (B, rec_width()) float64: the primal-dual point the sensitivity passes factorise at (layout in
           include/lafse3.h), which ``ocp_vjp`` turns into gradients later.  ``weights`` as ocp_sensitivity_w."""
         d, f64 = self.device, torch.float64
-        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
+        B, *inputs, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
         w = _weight_rows(weights, B, d)
-        N = self.horizon
-        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,)}
-        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
-        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
-        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
+        out = _solve_outputs(B, self.horizon, want, f64, d)
         # zeros: the entries of stages beyond the horizon are not written
         out["rec"] = torch.zeros((B, self.rec_width()), dtype=f64, device=d)
-        check(self._L.lafse3_ocp_solve_rec(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
-                                           _ptr(w), _ptr(out["x"]), _ptr(out["u"]), _ptr(out["lam"]),
-                                           _ptr(out["cost"]), _ptr(out["status"]), _ptr(out["iters"]),
-                                           _ptr(out["rec"]), self._stream()), "lafse3_ocp_solve_rec")
-        return {k: v for k, v in out.items() if v is not None}
+        return self._solve_call("lafse3_ocp_solve_rec", B, inputs, out, before=(_ptr(w),), after=(_ptr(out["rec"]),))
 
     def ocp_solve_warm(self, ini_state, goal, p_tra, a_tra, t, u_last=None, weights=None, rec=None, shift=0,
                        mu_init=None, retry=True, want=("x", "u", "lam", "cost"), opts=None, counters=None):
@@ -467,45 +439,32 @@ class Engine:
         ocp_solve_warm.  The problem is nonconvex: a warm start may end in another local optimum than the cold
         solve.  float64 only."""
         d, f64 = self.device, torch.float64
-        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
+        B, *inputs, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
         w = _weight_rows(weights, B, d)
-        N = self.horizon
-        if rec is None:
-            raise ValueError("rec is required")
-        rec = rec.detach().to(device=d, dtype=f64).contiguous()
-        if tuple(rec.shape) != (B, self.rec_width()):
-            raise ValueError(f"rec: expected ({B}, {self.rec_width()}), got {tuple(rec.shape)}")
+        rec = self._rec_rows(rec, B)
         o = _lib.default_warm_opts() if opts is None else opts
         o = _lib.WarmOpts(o.shift, o.mu_init, o.bound_push, o.bound_frac, o.mult_bound_push)
         o.shift = int(shift)
         if mu_init is not None:
             o.mu_init = float(mu_init)
-        shapes = {"x": (B, N + 1, NX), "u": (B, N, NU), "lam": (B, N, NX), "cost": (B,)}
-        out = {k: torch.empty(s, dtype=f64, device=d) if k in want else None for k, s in shapes.items()}
-        out["status"] = torch.empty((B,), dtype=torch.int32, device=d)
-        out["iters"] = torch.empty((B,), dtype=torch.int32, device=d)
+        out = _solve_outputs(B, self.horizon, want, f64, d)
         out["warm_status"] = torch.empty((B,), dtype=torch.int32, device=d)
         out["rec"] = torch.zeros((B, self.rec_width()), dtype=f64, device=d)
-        check(self._L.lafse3_ocp_solve_warm(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
-                                            _ptr(w), _ptr(rec), ctypes.byref(o), _ptr(out["x"]), _ptr(out["u"]),
-                                            _ptr(out["lam"]), _ptr(out["cost"]), _ptr(out["status"]),
-                                            _ptr(out["iters"]), _ptr(out["warm_status"]), _ptr(out["rec"]),
-                                            self._stream()), "lafse3_ocp_solve_warm")
+        res = self._solve_call("lafse3_ocp_solve_warm", B, inputs, out, before=(_ptr(w), _ptr(rec), ctypes.byref(o)),
+                               after=(_ptr(out["warm_status"]), _ptr(out["rec"])))
         if counters is not None:
-            counters.append(dict(self.last_counters(), **self.last_resto_counters(), kernel_ms=self.last_kernel_ms()))
+            counters.append(self._launch_counters())
         if retry:
-            failed = (out["status"] > 1) & (out["warm_status"] == 0)
+            failed = (res["status"] > 1) & (res["warm_status"] == 0)
             if int(failed.sum()) > 0:   # the one device-side count; the second launch only when it is non-zero
                 idx = failed.nonzero().squeeze(1)
-                cold = self.ocp_solve_rec(ini[idx], goal[idx], p[idx], a[idx], tt[idx],
-                                          None if ul is None else ul[idx], None if w is None else w[idx], want=want)
+                cold = self.ocp_solve_rec(*(None if v is None else v[idx] for v in (*inputs, w)), want=want)
                 if counters is not None:
-                    counters.append(dict(self.last_counters(), **self.last_resto_counters(),
-                                         kernel_ms=self.last_kernel_ms()))
+                    counters.append(self._launch_counters())
                 for k, v in cold.items():
-                    out[k][idx] = v
-                out["warm_status"][idx] = 2
-        return {k: v for k, v in out.items() if v is not None}
+                    res[k][idx] = v
+                res["warm_status"][idx] = 2
+        return res
 
     def ocp_vjp(self, ini_state, goal, p_tra, a_tra, t, u_last, weights, rec, g_x=None, g_u=None,
                 groups=("theta", "ini", "goal", "weights")):
@@ -517,24 +476,19 @@ class Engine:
         under the same params.  g_x (B, N+1, 13), g_u (B, N, 4): the loss gradients w.r.t. x and u (None = zero).
         Returns {grad, sens_status (B,) int32: 0 ok, 1 the recorded solve ended with status > 1, 2 wrong inertia at
         the optimum, 3 the record's horizon is not this engine's (rows != 0 are zero), columns}.  float64 only."""
-        mask, columns = _groups_w(groups)
+        mask, columns = _parse_groups(groups, _lib.SENS_GROUPS_W)
         d, f64 = self.device, torch.float64
-        B, ini, goal, p, a, tt, ul, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
+        B, *inputs, _ = _solve_inputs(d, f64, ini_state, goal, p_tra, a_tra, t, u_last)
         w = _weight_rows(weights, B, d)
         N = self.horizon
-        if rec is None:
-            raise ValueError("rec is required")
-        rec = rec.detach().to(device=d, dtype=f64).contiguous()
-        if tuple(rec.shape) != (B, self.rec_width()):
-            raise ValueError(f"rec: expected ({B}, {self.rec_width()}), got {tuple(rec.shape)}")
+        rec = self._rec_rows(rec, B)
         gx = _dev_tensor(g_x, (N + 1, NX), f64, d, "g_x", allow_none=True)
         gu = _dev_tensor(g_u, (N, NU), f64, d, "g_u", allow_none=True)
         gx, gu = _same_batch(B, g_x=gx, g_u=gu)
         grad = torch.empty((B, len(columns)), dtype=f64, device=d)
         ss = torch.empty((B,), dtype=torch.int32, device=d)
-        check(self._L.lafse3_ocp_vjp(self._ctx, B, _ptr(ini), _ptr(goal), _ptr(p), _ptr(a), _ptr(tt), _ptr(ul),
-                                     _ptr(w), _ptr(rec), _ptr(gx), _ptr(gu), mask, _ptr(grad), _ptr(ss),
-                                     self._stream()), "lafse3_ocp_vjp")
+        check(self._L.lafse3_ocp_vjp(self._ctx, B, *map(_ptr, inputs), _ptr(w), _ptr(rec), _ptr(gx), _ptr(gu), mask,
+                                     _ptr(grad), _ptr(ss), self._stream()), "lafse3_ocp_vjp")
         return {"grad": grad, "sens_status": ss, "columns": columns}
 
     def objective(self, ini_state, goal, gate12, p_tra, a_tra, t, u_last=None):

@@ -16,20 +16,17 @@ The step is dumped before and after the refinement: the unrefined step runs forw
 record, the refined one runs backward_chain and forward_chain on the refinement right-hand sides.  `ipm_kernel_dump`
 instantiates the same linear_solve as the production kernel (see test_gpu_newton.py).
 """
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")   # tests/newton.py needs it
 
-import newton  # noqa: E402
 import newton_cases as NC  # noqa: E402
+from newton_gpu import gpu_run, step_solves_the_dense_system  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 10.0                       # test_gpu_newton.py's
 HORIZONS = (4, 5, 6, 8, 11, 12)
 _cache = {}
-_engines = {}
 
 
 @pytest.fixture(scope="module")
@@ -38,37 +35,6 @@ def batch():
         pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
     from learningagileflight_se3_amd import scenario as S
     return S.synthetic_batch(64, seed=2025)
-
-
-def engine(N):
-    if N not in _engines:
-        from learningagileflight_se3_amd.engine import Engine
-        _engines[N] = Engine(horizon=N)
-    return _engines[N]
-
-
-def gpu_run(prob, N, k, after_refine, idx):
-    e = engine(N)
-    idx = np.asarray(idx)
-    rec = torch.full((len(idx), newton.DUMP_W), NC.SENTINEL, dtype=torch.float64, device=e.device)
-    tr = torch.zeros((len(idx), k + 1, 16), dtype=torch.float64, device=e.device)
-    p = e.params
-    saved = p.max_iter
-    p.max_iter = k + 1
-    e.set_params(p)
-    e.debug_dump(rec, k, bool(after_refine))
-    e.debug_trace(tr, k + 1)
-    try:
-        e.ocp_solve(prob["ini"][idx], prob["goal"][idx], prob["p"][idx], prob["a"][idx], prob["t"][idx],
-                    u_last=prob["ulast"][idx])
-        torch.cuda.synchronize()
-        resto = e.last_resto_counters()["resto_entries"]
-    finally:
-        e.debug_dump(None)
-        e.debug_trace(None)
-        p.max_iter = saved
-        e.set_params(p)
-    return rec.cpu().numpy(), tr.cpu().numpy(), resto
 
 
 def horizon(batch, N):
@@ -86,18 +52,7 @@ def test_step_solves_the_dense_system(batch, N):
     unrefined steps is at most MARGIN times the oracle's on the same cases."""
     prob, ocases, gcases = horizon(batch, N)
     assert set(ocases) == set(gcases)
-    for (s, k), c in gcases.items():
-        assert c["resto"] == [0, 0], (N, s, k, "restoration phase entered")
-        assert np.all(c["trace"][:k + 1, 0] > 0.0), (N, s, k)
-    g = NC.ratios("gpu-chain", prob, N, gcases)
-    o = NC.ratios("oracle-chain", prob, N, ocases)
-    gpre, gpost = max(v[0] for v in g.values()), max(v[1] for v in g.values())
-    opre, opost = max(v[0] for v in o.values()), max(v[1] for v in o.values())
-    print(f"N={N}: {len(g)} cases, largest residual ratio unrefined GPU {gpre:.3e} oracle {opre:.3e}, "
-          f"refined GPU {gpost:.3e} oracle {opost:.3e}")
-    assert all(v[1] <= 1e-5 for v in g.values()), g           # IPOPT's residual_ratio_singular
-    assert gpost <= MARGIN * opost, (gpost, opost)
-    assert gpre <= MARGIN * opre, (gpre, opre)
+    step_solves_the_dense_system(f"N={N}", "-chain", prob, N, ocases, gcases)
 
 
 @pytest.mark.parametrize("N", HORIZONS)

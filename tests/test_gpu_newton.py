@@ -87,15 +87,12 @@ torch = pytest.importorskip("torch")   # tests/newton.py needs it
 import generic_params as GP  # noqa: E402
 import newton  # noqa: E402
 import newton_cases as NC  # noqa: E402
+from newton_gpu import MARGIN, gpu_run, gpu_solve, step_solves_the_dense_system  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 10.0      # GPU against oracle, largest residual ratio over the cases: a different summation order (MFMA
-                   # k-steps, FMA contraction, the rsq-based pivot) shifts rounding by small factors; a wrong matrix
-                   # entry leaves the ratio orders of magnitude higher
 OTHER_SETS = tuple(n for n in GP.SETS if n != "default")   # the tests below keep their names at the default set
 _cache = {}
-_engines = {}
 
 
 @pytest.fixture(scope="module")
@@ -104,45 +101,6 @@ def batch():
         pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
     from learningagileflight_se3_amd import scenario as S
     return S.synthetic_batch(64, seed=2025)
-
-
-def engine(N, prm=None):
-    if (N, prm) not in _engines:
-        from learningagileflight_se3_amd.engine import Engine
-        _engines[(N, prm)] = Engine(horizon=N, **({} if prm is None else prm.fields()))
-    return _engines[(N, prm)]
-
-
-def gpu_solve(prob, N, idx, max_iter):
-    e = engine(N, prob["prm"])
-    p = e.params
-    saved = p.max_iter
-    p.max_iter = max_iter
-    e.set_params(p)
-    try:
-        out = e.ocp_solve(prob["ini"][idx], prob["goal"][idx], prob["p"][idx], prob["a"][idx], prob["t"][idx],
-                          u_last=prob["ulast"][idx])
-        torch.cuda.synchronize()
-    finally:
-        p.max_iter = saved
-        e.set_params(p)
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def gpu_run(prob, N, k, after_refine, idx):
-    e = engine(N, prob["prm"])
-    idx = np.asarray(idx)
-    rec = torch.full((len(idx), newton.DUMP_W), NC.SENTINEL, dtype=torch.float64, device=e.device)
-    tr = torch.zeros((len(idx), k + 1, 16), dtype=torch.float64, device=e.device)
-    e.debug_dump(rec, k, bool(after_refine))
-    e.debug_trace(tr, k + 1)
-    try:
-        gpu_solve(prob, N, idx, k + 1)
-        resto = e.last_resto_counters()["resto_entries"]
-    finally:
-        e.debug_dump(None)
-        e.debug_trace(None)
-    return rec.cpu().numpy(), tr.cpu().numpy(), resto
 
 
 def horizon(batch, N, pset="default"):
@@ -161,18 +119,7 @@ def test_step_solves_the_dense_system(batch, N, pset="default"):
     refined and of the unrefined steps is at most MARGIN times the oracle's on the same cases."""
     prob, ocases, gcases = horizon(batch, N, pset)
     assert set(ocases) == set(gcases)
-    for (s, k), c in gcases.items():
-        assert c["resto"] == [0, 0], (N, s, k, "restoration phase entered")
-        assert np.all(c["trace"][:k + 1, 0] > 0.0), (N, s, k)
-    g = NC.ratios("gpu/" + pset, prob, N, gcases)
-    o = NC.ratios("oracle/" + pset, prob, N, ocases)
-    gpre, gpost = max(v[0] for v in g.values()), max(v[1] for v in g.values())
-    opre, opost = max(v[0] for v in o.values()), max(v[1] for v in o.values())
-    print(f"{pset} N={N}: {len(g)} cases, largest residual ratio unrefined GPU {gpre:.3e} oracle {opre:.3e}, "
-          f"refined GPU {gpost:.3e} oracle {opost:.3e}")
-    assert all(v[1] <= 1e-5 for v in g.values()), g           # IPOPT's residual_ratio_singular
-    assert gpost <= MARGIN * opost, (gpost, opost)
-    assert gpre <= MARGIN * opre, (gpre, opre)
+    step_solves_the_dense_system(f"{pset} N={N}", "/" + pset, prob, N, ocases, gcases)
 
 
 @pytest.mark.parametrize("N", NC.HORIZONS)

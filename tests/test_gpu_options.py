@@ -33,6 +33,8 @@ import yardstick
 
 torch = pytest.importorskip("torch")
 
+from newton_gpu import decisions, oracle_traced  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 MIN_SAMPLES = 2
@@ -64,28 +66,6 @@ def problem(batch, N, idx):
     t = d[:, 6].copy() if N == 50 else np.full(len(i), 0.5 * N * 0.1)
     return {"ids": i, "ini": batch["ini"][i], "goal": batch["goal"][i], "p": d[:, :3], "a": d[:, 3:6],
             "q": np.stack([O.rd2quat(a) for a in d[:, 3:6]]), "t": t}
-
-
-def oracle_traced(prob, params, TI=None):
-    """(solve, trace (B, TI, 16)) of the oracle's strict build; TI defaults to the longest solve + 1."""
-    from oracle import oracle as O
-    args = tuple(prob[k] for k in ("ini", "goal", "p", "q", "t"))
-    r = O.solve(*args, params=params)
-    TI = int(r["iters"].max()) + 1 if TI is None else TI
-    buf = np.zeros((len(r["iters"]), TI, 16))
-    O.debug_trace(buf, TI)
-    try:
-        O.solve(*args, params=params)
-    finally:
-        O.debug_trace(None, 0)
-    return r, buf
-
-
-def decisions(tr):
-    """The decision words of a trace: mu, delta_w, accepted, filter size, number of step halvings."""
-    with np.errstate(divide="ignore", invalid="ignore"):
-        h = np.where(tr[:, :, 7] > 0, np.round(np.log2(tr[:, :, 5] / tr[:, :, 7])), -1.0)
-    return np.concatenate([tr[:, :, [0, 8, 9, 10]], h[:, :, None]], axis=2)
 
 
 def admit(prob, N, opts):

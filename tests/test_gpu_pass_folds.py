@@ -61,16 +61,14 @@ import yardstick
 torch = pytest.importorskip("torch")   # tests/newton.py needs it
 
 import generic_params as GP  # noqa: E402
-import newton  # noqa: E402
 import newton_cases as NC  # noqa: E402
+from newton_gpu import decisions, engine, gpu_run, oracle_traced, step_solves_the_dense_system  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 10.0                         # test_gpu_newton.py's
 SAMPLES = tuple(range(4, 12))         # 8 instances per launch
 SOC_SAMPLES = (1, 5, 14, 21, 22, 24, 34, 35)
 WATCHDOG = {1: (5, 14, 22, 24, 34, 53, 54, 0), 3: (34, 54, 5, 14)}   # option value -> samples
-_engines = {}
 
 
 @pytest.fixture(scope="module")
@@ -79,38 +77,6 @@ def batch():
         pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
     from learningagileflight_se3_amd import scenario as S
     return S.synthetic_batch(64, seed=2025)
-
-
-def engine(N, fields=()):
-    if (N, fields) not in _engines:
-        from learningagileflight_se3_amd.engine import Engine
-        _engines[(N, fields)] = Engine(horizon=N, **dict(fields))
-    return _engines[(N, fields)]
-
-
-def gpu_run(prob, N, k, after_refine, idx):
-    """newton_cases backend: the samples idx solved up to iteration k with the dump of iteration k and the trace armed."""
-    e = engine(N, () if prob["prm"] is None else tuple(sorted(prob["prm"].fields().items())))
-    idx = np.asarray(idx)
-    rec = torch.full((len(idx), newton.DUMP_W), NC.SENTINEL, dtype=torch.float64, device=e.device)
-    tr = torch.zeros((len(idx), k + 1, 16), dtype=torch.float64, device=e.device)
-    p = e.params
-    saved = p.max_iter
-    p.max_iter = k + 1
-    e.set_params(p)
-    e.debug_dump(rec, k, bool(after_refine))
-    e.debug_trace(tr, k + 1)
-    try:
-        e.ocp_solve(prob["ini"][idx], prob["goal"][idx], prob["p"][idx], prob["a"][idx], prob["t"][idx],
-                    u_last=prob["ulast"][idx])
-        torch.cuda.synchronize()
-        resto = e.last_resto_counters()["resto_entries"]
-    finally:
-        e.debug_dump(None)
-        e.debug_trace(None)
-        p.max_iter = saved
-        e.set_params(p)
-    return rec.cpu().numpy(), tr.cpu().numpy(), resto
 
 
 def dense_check(batch, N, pset, last_iteration):
@@ -126,19 +92,7 @@ def dense_check(batch, N, pset, last_iteration):
         ocases = {c: v for c, v in ocases.items() if c[1] > 0}
         gcases = {c: v for c, v in gcases.items() if c[1] > 0}
     assert set(ocases) == set(gcases) and len(gcases) >= 2 * len(SAMPLES)
-    for (s, k), c in gcases.items():
-        assert c["resto"] == [0, 0], (N, s, k, "restoration phase entered")
-        assert np.all(c["trace"][:k + 1, 0] > 0.0), (N, s, k)
-    tag = f"folds/{pset}"
-    g = NC.ratios("gpu/" + tag, prob, N, gcases)
-    o = NC.ratios("oracle/" + tag, prob, N, ocases)
-    gpre, gpost = max(v[0] for v in g.values()), max(v[1] for v in g.values())
-    opre, opost = max(v[0] for v in o.values()), max(v[1] for v in o.values())
-    print(f"{pset} N={N}: {len(g)} cases, largest residual ratio unrefined GPU {gpre:.3e} oracle {opre:.3e}, "
-          f"refined GPU {gpost:.3e} oracle {opost:.3e}")
-    assert all(v[1] <= 1e-5 for v in g.values()), g
-    assert gpost <= MARGIN * opost, (gpost, opost)
-    assert gpre <= MARGIN * opre, (gpre, opre)
+    step_solves_the_dense_system(f"{pset} N={N}", f"/folds/{pset}", prob, N, ocases, gcases)
     NC.structure(prob, N, gcases)
 
 
@@ -162,21 +116,6 @@ def problem(batch, idx):
             "q": np.stack([O.rd2quat(a) for a in d[:, 3:6]]), "t": d[:, 6].copy()}
 
 
-def oracle_traced(prob, params, TI=None):
-    """(solve, trace (B, TI, 16)) of the oracle's strict build; TI defaults to the longest solve + 1."""
-    from oracle import oracle as O
-    args = tuple(prob[k] for k in ("ini", "goal", "p", "q", "t"))
-    r = O.solve(*args, params=params)
-    TI = int(r["iters"].max()) + 1 if TI is None else TI
-    buf = np.zeros((len(r["iters"]), TI, 16))
-    O.debug_trace(buf, TI)
-    try:
-        O.solve(*args, params=params)
-    finally:
-        O.debug_trace(None, 0)
-    return r, buf
-
-
 def option_changes(prob, opts, other):
     """Oracle alone: (solve with opts, its trace, per sample whether the trace differs from the solve with `other`)."""
     from oracle import oracle as O
@@ -194,13 +133,6 @@ def back_at_stored_point(tr, iters):
     return [j for j in range(2, int(iters)) if any(np.array_equal(tr[j, 2:5], tr[i, 2:5]) for i in range(j - 1))]
 
 
-def decisions(tr):
-    """The decision words of a trace (test_gpu_options.py): mu, delta_w, accepted, filter size, step halvings."""
-    with np.errstate(divide="ignore", invalid="ignore"):
-        h = np.where(tr[:, :, 7] > 0, np.round(np.log2(tr[:, :, 5] / tr[:, :, 7])), -1.0)
-    return np.concatenate([tr[:, :, [0, 8, 9, 10]], h[:, :, None]], axis=2)
-
-
 def solve_matches_oracle(label, prob, opts, ref, otr):
     """The criteria of test_gpu_parity.py's test_ocp_solve_matches_oracle_and_is_kkt on the solves of prob, and on the
     solves that the rounding yardstick admits (the oracle's FMA build takes its strict build's decisions) also the
@@ -210,7 +142,7 @@ def solve_matches_oracle(label, prob, opts, ref, otr):
     on 54 at watchdog = 3, and no iteration count does)."""
     from oracle import oracle as O
     import kkt
-    e = engine(50, tuple(sorted(opts.items())))
+    e = engine(50, opts)
     gtr = torch.zeros((len(prob["ids"]), otr.shape[1], 16), dtype=torch.float64, device=e.device)
     e.debug_trace(gtr, otr.shape[1])
     try:

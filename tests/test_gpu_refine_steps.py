@@ -38,8 +38,8 @@ torch = pytest.importorskip("torch")   # tests/newton.py needs it
 
 import newton  # noqa: E402
 import newton_cases as NC  # noqa: E402
+from newton_gpu import MARGIN, gpu_run  # noqa: E402
 
-MARGIN = 10.0                       # test_gpu_newton.py's
 HORIZONS = (1, 2, 3, 50)
 KINDS = ("reverted", "kept", "several")
 # cases per horizon and kind.  Reverted steps are the rare ones on the GPU (a ratio that rounding noise alone moves
@@ -52,7 +52,6 @@ EXPECT = {1: (256, {"reverted": 6, "kept": 2, "several": 0}),
           50: (64, {"reverted": 6, "kept": 2, "several": 0})}
 _chosen = {}
 _cache = {}
-_engines = {}
 _ran = {}
 
 
@@ -106,37 +105,6 @@ def choose(N):
     pos = {s: j for j, s in enumerate(samples)}
     _chosen[N] = (B, problem(batch, N, samples), {kd: [(pos[s], k) for s, k in v] for kd, v in picked.items()})
     return _chosen[N]
-
-
-def engine(N):
-    if N not in _engines:
-        from learningagileflight_se3_amd.engine import Engine
-        _engines[N] = Engine(horizon=N)
-    return _engines[N]
-
-
-def gpu_run(prob, N, k, after_refine, idx):
-    e = engine(N)
-    idx = np.asarray(idx)
-    rec = torch.full((len(idx), newton.DUMP_W), NC.SENTINEL, dtype=torch.float64, device=e.device)
-    tr = torch.zeros((len(idx), k + 1, 16), dtype=torch.float64, device=e.device)
-    p = e.params
-    saved = p.max_iter
-    p.max_iter = k + 1
-    e.set_params(p)
-    e.debug_dump(rec, k, bool(after_refine))
-    e.debug_trace(tr, k + 1)
-    try:
-        e.ocp_solve(prob["ini"][idx], prob["goal"][idx], prob["p"][idx], prob["a"][idx], prob["t"][idx],
-                    u_last=prob["ulast"][idx])
-        torch.cuda.synchronize()
-        resto = e.last_resto_counters()["resto_entries"]
-    finally:
-        e.debug_dump(None)
-        e.debug_trace(None)
-        p.max_iter = saved
-        e.set_params(p)
-    return rec.cpu().numpy(), tr.cpu().numpy(), resto
 
 
 def collect(run, prob, N, wanted):
