@@ -279,13 +279,13 @@ def debug_trace(buf=None, iters=0, fast=False):
     lib(fast).orc_debug_trace(_ptr(buf), int(iters))
 
 
-def debug_dump(buf=None, it=-1, after_refine=False):
+def debug_dump(buf=None, it=-1, after_refine=False, fast=False):
     """Debug: Newton step [dx 51x13 | du 50x4 | lam+ 50x13] of iteration `it` and the iterate it was computed at
     [x 51x13 | u 50x4 | lam 50x13 | zLu 50x4 | zUu 50x4 | zLw 51x3 | zUw 51x3] into buf (B, DUMP_W = 3732), the
-    record of lafse3_debug_dump (lafse3.h)."""
+    record of lafse3_debug_dump (lafse3.h).  fast=True arms the -O3 / FMA build (solve(fast=True))."""
     global _dump_keep
     _dump_keep = buf
-    lib().orc_debug_dump(_ptr(buf), int(it), int(after_refine))
+    lib(fast).orc_debug_dump(_ptr(buf), int(it), int(after_refine))
 
 
 def debug_dump_resto(buf=None, entry=-1, it=-1, after_refine=False):

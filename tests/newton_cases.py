@@ -49,20 +49,25 @@ def problem(batch, N, prm=None, t_scale=1.0, samples=SAMPLES):
             "q": np.stack([O.rd2quat(a) for a in d[:, 3:6]]), "t": t, "ulast": ul}
 
 
-def oracle_run(prob, N, k, after_refine, idx):
+def oracle_run(prob, N, k, after_refine, idx, fast=False):
+    """The oracle's strict build, or with fast=True its -O3 / FMA build (the rounding yardstick's other side)."""
     from oracle import oracle as O
     idx = np.asarray(idx)
     rec = np.full((len(idx), newton.DUMP_W), SENTINEL)
     tr = np.zeros((len(idx), k + 1, 16))
-    O.debug_dump(rec, k, after_refine)
-    O.debug_trace(tr, k + 1)
+    O.debug_dump(rec, k, after_refine, fast=fast)
+    O.debug_trace(tr, k + 1, fast=fast)
     try:
         O.solve(prob["ini"][idx], prob["goal"][idx], prob["p"][idx], prob["q"][idx], prob["t"][idx],
-                ulast=prob["ulast"][idx], params=oracle_params(prob.get("prm"), horizon=N, max_iter=k + 1))
+                ulast=prob["ulast"][idx], params=oracle_params(prob.get("prm"), horizon=N, max_iter=k + 1), fast=fast)
     finally:
-        O.debug_dump(None)
-        O.debug_trace(None, 0)
+        O.debug_dump(None, fast=fast)
+        O.debug_trace(None, 0, fast=fast)
     return rec, tr, None
+
+
+def oracle_run_fma(prob, N, k, after_refine, idx):
+    return oracle_run(prob, N, k, after_refine, idx, fast=True)
 
 
 def oracle_full(prob, N):
@@ -99,6 +104,26 @@ def collect(run, prob, N, iters):
             cases[(s, k)] = {"pre": pre, "post": post, "point": pt0, "pad": np.concatenate([pad0, pad1]),
                              "trace": side[1][1][j], "resto": [side[0][2], side[1][2]]}
     return cases
+
+
+def collect_pairs(run, prob, N, cases, launch=4):
+    """Iterations k and k + 1 of every (sample, k) of `cases` through backend `run`, refined steps: per k, launches of
+    at most `launch` samples with max_iter k + 1 and k + 2.  Returns {(sample, k): dict(step, point: iteration k;
+    next_step, next_point: iteration k + 1; pad: the padding entries of both records; first (k + 1, 16), trace
+    (k + 2, 16): the traces of the two launches)}."""
+    out = {}
+    for k in sorted({k for _, k in cases}):
+        idx = sorted(s for s, kk in cases if kk == k)
+        for o in range(0, len(idx), launch):
+            part = idx[o:o + launch]
+            rec0, tr0, _ = run(prob, N, k, 1, part)
+            rec1, tr1, _ = run(prob, N, k + 1, 1, part)
+            for j, s in enumerate(part):
+                step, point, pad0 = newton.split_record(rec0[j], N)
+                nstep, npoint, pad1 = newton.split_record(rec1[j], N)
+                out[(s, k)] = {"step": step, "point": point, "next_step": nstep, "next_point": npoint,
+                               "pad": np.concatenate([pad0, pad1]), "first": tr0[j], "trace": tr1[j]}
+    return out
 
 
 _systems = {}
