@@ -240,6 +240,10 @@ struct __align__(16) Smem {
     Ctl C;
     double goal[3], ptra[3], ulast[4];
     double col[4];
+    // per-lane index tables of the factorisation sweep (riccati_mfma.inc): functions of the lane alone, written once
+    // per workgroup ahead of the instance loop (init_mf_tables) and read back by every sweep
+    alignas(16) unsigned mfp[WAVE][4];       // packed-P store offsets of the lane's four P' entries
+    unsigned short mfo[14][WAVE];            // Smem byte offsets: its gathers of G, H~ [4] and h~ [2], four LDS targets
 #ifdef LAFSE3_FAC_CHECK
     double facd[4];                          // diagnostic: max relative difference MFMA vs VALU sweep (fac_check)
 #endif
@@ -2748,6 +2752,7 @@ __device__ __attribute__((always_inline)) inline Smem &instance_smem()
 __global__ __launch_bounds__(64, 1) void ipm_kernel(KernelArgs A)
 {
     Smem &S = instance_smem();
+    init_mf_tables(S);   // the sweeps' per-lane tables: once per workgroup, every instance of the slot reads them
     // one call site of run_instance (a second inlined copy doubles the code and its spill frame);
     // without A.persistent (trajectory scoring) workgroup b takes instance b once
     gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
@@ -2786,6 +2791,7 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel(KernelArgs A)
 __global__ __launch_bounds__(64, 1) void ipm_kernel_dump(KernelArgs A, RestoDumpArgs Z)
 {
     Smem &S = instance_smem();
+    init_mf_tables(S);
     gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
     for (;;) {
         unsigned long long v = 0ull;
@@ -2806,6 +2812,7 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_dump(KernelArgs A, RestoDump
 __global__ __launch_bounds__(64, 1) void ipm_kernel_ext(KernelArgs A, ExtArgs Z)
 {
     Smem &S = instance_smem();
+    init_mf_tables(S);
     gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
     for (;;) {
         unsigned long long v = 0ull;
@@ -2825,6 +2832,7 @@ __global__ __launch_bounds__(64, 1) void ipm_kernel_ext(KernelArgs A, ExtArgs Z)
 __global__ __launch_bounds__(64, 1) void ipm_kernel_warm(KernelArgs A, ExtArgs Z, WarmArgs W)
 {
     Smem &S = instance_smem();
+    init_mf_tables(S);
     gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
     for (;;) {
         unsigned long long v = 0ull;

@@ -150,6 +150,73 @@ constexpr int MF_QU = MF_TR + 12 * MF_TRS;   // [16] the u~ lanes' Qux column / 
 static_assert(MF_QU + 16 <= NA * GST + NZ * GST && MF_QU % 2 == 0, "MFMA sweep LDS inside the W / M union");
 static_assert(TB_W <= 160 && MF_ROW + 168 <= MF_QB && MF_QB % 2 == 0 && MF_TV % 2 == 0 && MF_DUM % 2 == 0, "LDS map");
 
+// The sweep's per-lane tables in LDS (Smem::mfo, Smem::mfp), built once per workgroup: the kernels are persistent
+// and the tables depend on the lane alone, so every sweep of every instance reads them back with a few ds_read
+// instead of rebuilding them from c_mf (seven constant-memory loads, a wait for them, the slot -> address arithmetic
+// of 18 entries per lane) and from nested selects on the lane index (compiled to exec-mask branches).  All of mfo is
+// stored ready to use, as 16-bit byte offsets from Smem: the gathers of G and H~ (four each), of h~ (2), and the
+// lane's LDS targets qx_dst, q_src, tv_dst and its kbuf row.
+constexpr int MFO_G = 0, MFO_H = 4, MFO_HC = 8, MFO_HU = 9, MFO_QX = 10, MFO_QS = 11, MFO_TV = 12, MFO_KB = 13;
+__host__ __device__ constexpr unsigned mf_w_off(int e) { return (unsigned)(offsetof(Smem, W) + 8 * e); }   // &S.W[e]
+__host__ __device__ constexpr unsigned mf_row_off(int slot) { return mf_w_off(MF_ROW + (slot < 0 ? 160 : slot)); }
+static_assert(sizeof(Smem) < 65536, "Smem offsets fit 16 bits");
+// a table entry as a 32-bit offset.  The empty asm keeps the zero extension at the load, where ds_read_u16 does it: left
+// to the block of the first use it was a v_and per entry and sweep
+__device__ inline unsigned mf_ld16(const unsigned short &e)
+{
+    unsigned v = e;
+    asm volatile("" : "+v"(v));
+    return v;
+}
+__device__ inline void init_mf_tables(Smem &S)
+{
+    const int lane = lane_id();
+    const int g = lane >> 4, c = lane & 15;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        S.mfo[MFO_G + s][lane] = (unsigned short)mf_row_off(c_mf.g[lane][s]);
+        S.mfo[MFO_H + s][lane] = (unsigned short)mf_row_off(c_mf.h[lane][s]);
+        const int pe = c_mf.pst[lane][s];
+        S.mfp[lane][s] = pe < 0 ? MF_OOB : (unsigned)(WS_PST + pe) * 8u;
+    }
+    S.mfo[MFO_HC][lane] = (unsigned short)mf_row_off(c_mf.hc[c]);
+    S.mfo[MFO_HU][lane] = (unsigned short)mf_row_off(c_mf.hu[c]);
+    // LDS targets of the stage's branch-free stores: Qux(u, r0) / g_u (lanes of columns 12..15), p12' / p' transposed
+    // (group 0), the solved column's record row (lane 16: the r0 column, lane 17: k)
+    const int dum = MF_DUM + lane;   // write-only: neighbouring lanes' slots may overlap
+    S.mfo[MFO_QX][lane] = (unsigned short)mf_w_off((c >= 12) ? MF_QB + 64 + (c - 12) : dum);
+    S.mfo[MFO_TV][lane] = (unsigned short)mf_w_off((g == 0) ? MF_TV + (c & 3) * 4 + (c >> 2) : dum);
+    // Qux column c (u~ columns: H~(u~, u) e); lane 16 takes M(u, r0) instead, so that its p12' / p' are the r0
+    // corner p22' / p_r0' (lane 16's own column is lane 0's, whose results it duplicates otherwise)
+    S.mfo[MFO_QS][lane] = (unsigned short)mf_w_off((lane == 16) ? MF_QB + 64 : ((c < 12) ? MF_QB + 4 * c : MF_QU + 4 * (c - 12)));
+    S.mfo[MFO_KB][lane] = (unsigned short)(offsetof(Smem, kbuf) + 8 * ((lane == 16) ? 0 : ((lane == 17) ? RC_KF : mf_x(c) * NU)));
+    sync();
+}
+// c~ in row-group layout needs no table: c~(4 s + g) of the x rows (s < 3) is one lane offset plus 32 s bytes, and
+// register 3 (the u~ rows) is the row's zero slot
+__host__ __device__ constexpr bool mf_ct_is_strided()
+{
+    const MfTab T = make_mftab();
+    for (int l = 0; l < WAVE; ++l)
+        for (int s = 0; s < 4; ++s)
+            if (T.ct[l][s] != (s < 3 ? TB_c + 1 + (l >> 4) + 4 * s : MF_ZERO)) return false;
+    return true;
+}
+static_assert(mf_ct_is_strided(), "c~ gather of the MFMA stage: TB_c + 1 + g + 4 s, zero in register 3");
+// The delta_w flags need no table: H~'s flagged entries are its diagonal, which lane (g, c) holds in register s
+// where 4 s + g == c, and the u diagonal (flag 2) is columns 12..15, that is s == 3.
+__host__ __device__ constexpr bool mf_flags_are_diagonal()
+{
+    const MfTab T = make_mftab();
+    for (int l = 0; l < WAVE; ++l)
+        for (int s = 0; s < 4; ++s) {
+            const bool d = (l & 15) - (l >> 4) == 4 * s;
+            if ((T.hf[l][s] != 0) != d || (T.hf[l][s] == 2) != (d && s == 3)) return false;
+        }
+    return true;
+}
+static_assert(mf_flags_are_diagonal(), "delta_w flags of the MFMA stage: the diagonal, u in register 3");
+
 // diagnostic sub-phase timers of the stage (timer build with -DLAFSE3_PT_FINE: slots 16..23, tools/gpu_timers_fine.py)
 #if defined(LAFSE3_PT_FINE) && defined(LAFSE3_PHASE_TIMERS)
 #define PT_FINE(i) PT_END(S, 16 + (i))
@@ -179,37 +246,37 @@ __device__ __attribute__((always_inline)) inline int backward_mfma(const Model &
     load_row3(N - 1, r0, r1, r2);
     terminal(M, at, S, C, ws, dw, mode_lsq, 0);   // P_N, p_N -> S.P / S.p (x~ order), Pst[N-1], WS_PN
     double *L0 = S.W;   // sweep LDS base (MF_*)
-    auto rslot = [](int slot) { return MF_ROW + (slot < 0 ? 160 : slot); };
-    int og[4], oh[4], oc[4];
+    // the lane's tables from LDS (init_mf_tables): gather offsets in bytes from Smem, packed-P store offsets
+    char *Sb = (char *)&S;
+    auto lds = [&](unsigned off) { return *(const double *)(Sb + off); };
+    unsigned og[4], oh[4], oc[4];
     unsigned op[4];
     double e2[4], e12[4];
+    {
+        const uint4 pv = *(const uint4 *)S.mfp[lane];
+        op[0] = pv.x; op[1] = pv.y; op[2] = pv.z; op[3] = pv.w;
+    }
+    const unsigned ocb = mf_row_off(TB_c + 1) + 8u * (unsigned)g;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        og[s] = rslot(c_mf.g[lane][s]);
-        oh[s] = rslot(c_mf.h[lane][s]);
-        oc[s] = rslot(c_mf.ct[lane][s]);
-        const int pe = c_mf.pst[lane][s];
-        op[s] = pe < 0 ? MF_OOB : (unsigned)(WS_PST + pe) * 8u;
-        const int fl = c_mf.hf[lane][s];
-        e2[s] = (fl == 2) ? dw : 0.0;    // u diagonal: + delta_w (stage 0: x_0 is fixed)
-        e12[s] = (fl != 0) ? dw : 0.0;   // x and u diagonal: + delta_w (stages k >= 1)
+        og[s] = mf_ld16(S.mfo[MFO_G + s][lane]);
+        oh[s] = mf_ld16(S.mfo[MFO_H + s][lane]);
+        oc[s] = (s < 3) ? ocb + 32u * s : mf_row_off(MF_ZERO);
+        e12[s] = (c - g == 4 * s) ? dw : 0.0;   // x and u diagonal: + delta_w (stages k >= 1)
+        e2[s] = (s == 3) ? e12[s] : 0.0;        // u diagonal: + delta_w (stage 0: x_0 is fixed)
     }
-    const int ohc = rslot(c_mf.hc[c]), ohu = rslot(c_mf.hu[c]);
+    const unsigned ohc = mf_ld16(S.mfo[MFO_HC][lane]), ohu = mf_ld16(S.mfo[MFO_HU][lane]);
+    // the lane's LDS targets (init_mf_tables has what they are); the right-hand side is the Qux column except in
+    // lane 17, which solves for k from g_u
+    const unsigned qx_dst = mf_ld16(S.mfo[MFO_QX][lane]), q_src = mf_ld16(S.mfo[MFO_QS][lane]);
+    const unsigned tv_dst = mf_ld16(S.mfo[MFO_TV][lane]);
+    const unsigned kb_dst = mf_ld16(S.mfo[MFO_KB][lane]);
+    const unsigned rhs_src = (lane == 17) ? mf_w_off(MF_QB + 68) : q_src;
     const bool isx = c < 12;
     const double dt = M.dt;
     const double m2dt = (c == 2) ? dt : 0.0, r2dt = (g == 2) ? dt : 0.0;
     const double idm = (c >= 12) ? 1.0 : 0.0;   // W's u columns: + P(:, u~)
-    // LDS targets of the branch-free stores: Qux(u, r0) / g_u (lanes of columns 12..15), the solved column's record
-    // row (lane 16: the r0 column, lane 17: k), p12' / p' transposed (group 0)
-    const int dum = MF_DUM + lane;   // write-only: neighbouring lanes' slots may overlap
-    const int qx_dst = (c >= 12) ? MF_QB + 64 + (c - 12) : dum;
-    // Qux column c (u~ columns: H~(u~, u) e); lane 16 takes M(u, r0) instead, so that its p12' / p' are the r0
-    // corner p22' / p_r0' (lane 16's own column is lane 0's, whose results it duplicates otherwise)
-    const int q_src = (lane == 16) ? MF_QB + 64 : ((c < 12) ? MF_QB + 4 * c : MF_QU + 4 * (c - 12));
-    const int rhs_src = (lane == 16) ? MF_QB + 64 : ((lane == 17) ? MF_QB + 68 : ((c < 12) ? MF_QB + 4 * c : MF_QU + 4 * (c - 12)));
     const bool solve_col = lane != 16 && lane != 17;
-    const int tv_dst = (g == 0) ? MF_TV + (c & 3) * 4 + (c >> 2) : dum;
-    double *kb_dst = (lane == 16) ? &S.kbuf[0] : ((lane == 17) ? &S.kbuf[RC_KF] : &S.kbuf[mf_x(c) * NU]);
     auto put_row = [&](double t0, double t1, double t2) {
         L0[MF_ROW + lane] = t0;
         L0[MF_ROW + 64 + lane] = t1;
@@ -243,12 +310,12 @@ __device__ __attribute__((always_inline)) inline int backward_mfma(const Model &
     auto gather = [&](Pf &f) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            f.G[s] = L0[og[s]];
-            f.H[s] = L0[oh[s]];
-            f.Ct[s] = L0[oc[s]];
+            f.G[s] = lds(og[s]);
+            f.H[s] = lds(oh[s]);
+            f.Ct[s] = lds(oc[s]);
         }
-        f.hc = L0[ohc];
-        f.hu = L0[ohu];
+        f.hc = lds(ohc);
+        f.hu = lds(ohu);
         f.c16 = L0[MF_ROW + TB_c];
         f.hr0 = L0[MF_ROW + TB_h];
         f.Hr0 = L0[MF_ROW + TB_H];
@@ -343,8 +410,8 @@ __device__ __attribute__((always_inline)) inline int backward_mfma(const Model &
         PT_END(S, 13);
         // one solve per lane: column c of Qux (u~ columns: H~(u~, u) e), lane 16 M(u, r0), lane 17 g_u
         L0[MF_QB + c * 4 + g] = M3;   // Qux(g, c)
-        L0[qx_dst] = w21;             // M(u_a, r0)
-        L0[qx_dst + 4] = g11;         // g_u
+        *(double *)(Sb + qx_dst) = w21;        // M(u_a, r0)
+        *(double *)(Sb + qx_dst + 32) = g11;   // g_u
         sync();   // cross-lane LDS exchange: the compiler must not move the reads above the other lanes' writes
         double qc[4], tv[3];
         double x0, x1, x2, x3;
@@ -352,7 +419,7 @@ __device__ __attribute__((always_inline)) inline int backward_mfma(const Model &
             const double *T = L0 + MF_TR;
 #pragma unroll
             for (int s = 0; s < 3; ++s) tv[s] = T[min(c, 11) * MF_TRS + 4 * s + g];   // M(c, 4s + g)
-            const dvec2 *qp = (const dvec2 *)&L0[q_src], *rp = (const dvec2 *)&L0[rhs_src];
+            const dvec2 *qp = (const dvec2 *)(Sb + q_src), *rp = (const dvec2 *)(Sb + rhs_src);
             const dvec2 q0 = qp[0], q1 = qp[1], r0 = rp[0], r1 = rp[1];
             qc[0] = q0.x; qc[1] = q0.y; qc[2] = q1.x; qc[3] = q1.y;
             x0 = r0.x; x1 = r0.y; x2 = r1.x; x3 = r1.y;
@@ -390,7 +457,7 @@ __device__ __attribute__((always_inline)) inline int backward_mfma(const Model &
         PT_FINE(6);
         // factor record -> kbuf (x~ order): K^T row c + 1 (groups 1..3 duplicate group 0), row 0 = K(:, r0), k; L
         {
-            dvec2 *kb = (dvec2 *)kb_dst;
+            dvec2 *kb = (dvec2 *)(Sb + kb_dst);
             kb[0] = dv2(-x0, -x1);
             kb[1] = dv2(-x2, -x3);
             if (lane == 0) {
@@ -441,8 +508,8 @@ __device__ __attribute__((always_inline)) inline int backward_mfma(const Model &
             bst(pn, rs, ov, uni(k * 18 * 8));
         }
         // column -> row-group layout of p12', p' for the next stage
-        L0[tv_dst] = p12n;
-        L0[tv_dst + 16] = pn;
+        *(double *)(Sb + tv_dst) = p12n;
+        *(double *)(Sb + tv_dst + 128) = pn;
         sync();
         {
             const dvec2 *t0p = (const dvec2 *)&L0[MF_TV + g * 4], *t1p = (const dvec2 *)&L0[MF_TV + 16 + g * 4];

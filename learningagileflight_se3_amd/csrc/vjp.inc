@@ -171,6 +171,7 @@ __device__ __attribute__((always_inline)) inline void vjp_instance(const VjpArgs
 __global__ __launch_bounds__(64, 1) void vjp_kernel(VjpArgs A)
 {
     Smem &S = instance_smem();
+    init_mf_tables(S);   // linear_solve's factorisation sweep reads them
     gdouble *ws = (gdouble *)(A.ws + slot_id() * (int64_t)WS_SIZE);
     for (;;) {
         unsigned long long v = 0ull;
