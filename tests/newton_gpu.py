@@ -13,6 +13,7 @@ MARGIN = 10.0      # GPU against oracle, largest residual ratio over the cases: 
                    # k-steps, FMA contraction, the rsq-based pivot) shifts rounding by small factors; a wrong matrix
                    # entry leaves the ratio orders of magnitude higher
 _engines = {}
+_horizons = {}
 
 
 def engine(N, fields=None):
@@ -59,6 +60,15 @@ def gpu_run(prob, N, k, after_refine, idx):
             e.debug_dump(None)
             e.debug_trace(None)
     return rec.cpu().numpy(), tr.cpu().numpy(), resto
+
+
+def horizon(batch, N):
+    """(problem, oracle cases, GPU cases) of horizon N; the dumped iterations come from the oracle's full solve."""
+    if N not in _horizons:
+        prob = NC.problem(batch, N)
+        iters = NC.oracle_full(prob, N)["iters"]
+        _horizons[N] = (prob, NC.collect(NC.oracle_run, prob, N, iters), NC.collect(gpu_run, prob, N, iters))
+    return _horizons[N]
 
 
 def step_solves_the_dense_system(head, tag, prob, N, ocases, gcases):

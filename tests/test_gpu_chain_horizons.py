@@ -21,12 +21,11 @@ import pytest
 torch = pytest.importorskip("torch")   # tests/newton.py needs it
 
 import newton_cases as NC  # noqa: E402
-from newton_gpu import gpu_run, step_solves_the_dense_system  # noqa: E402
+from newton_gpu import horizon, step_solves_the_dense_system  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 HORIZONS = (4, 5, 6, 8, 11, 12)
-_cache = {}
 
 
 @pytest.fixture(scope="module")
@@ -35,15 +34,6 @@ def batch():
         pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
     from learningagileflight_se3_amd import scenario as S
     return S.synthetic_batch(64, seed=2025)
-
-
-def horizon(batch, N):
-    """(problem, oracle cases, GPU cases) of horizon N; the dumped iterations come from the oracle's full solve."""
-    if N not in _cache:
-        prob = NC.problem(batch, N)
-        iters = NC.oracle_full(prob, N)["iters"]
-        _cache[N] = (prob, NC.collect(NC.oracle_run, prob, N, iters), NC.collect(gpu_run, prob, N, iters))
-    return _cache[N]
 
 
 @pytest.mark.parametrize("N", HORIZONS)

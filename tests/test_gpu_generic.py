@@ -64,7 +64,7 @@ torch = pytest.importorskip("torch")
 import generic_params as GP  # noqa: E402
 import kkt  # noqa: E402
 import newton_cases as NC  # noqa: E402
-from test_gpu_parity import _grad_parity, _pmp_reference  # noqa: E402
+from parity_ref import grad_parity, pmp_reference  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -178,7 +178,7 @@ def grad_args(batch, B=16):
 
 
 def test_sol_gradient_fd_mode_matches_oracle(batch):
-    """grad_mode 0 on 16 samples at N = 50 against the oracle's sol_gradient under _grad_parity (test_gpu_parity.py)."""
+    """grad_mode 0 on 16 samples at N = 50 against the oracle's sol_gradient under parity_ref.grad_parity."""
     eng = engine()
     args = grad_args(batch)
     it = torch.full((16, 9), -1, dtype=torch.int32, device=eng.device)
@@ -191,7 +191,7 @@ def test_sol_gradient_fd_mode_matches_oracle(batch):
     o8, s9, it = o8.cpu().numpy(), s9.cpu().numpy(), it.cpu().numpy()
     assert np.all(s9 <= 1), s9
     assert np.count_nonzero(o8[:, :7]) >= 0.75 * o8[:, :7].size     # a gradient, not clipped-away zeros
-    _grad_parity(o8, s9, it, args, "generic set, FD mode", params=oracle_params(grad_mode=0))
+    grad_parity(o8, s9, it, args, "generic set, FD mode", params=oracle_params(grad_mode=0))
 
 
 def _ift_mode_against_oracle(args, label, resolvable_only=False):
@@ -282,7 +282,7 @@ def test_sol_gradient_nlp_inputs_match_oracle(batch):
 
 
 def test_pmp_costates_match_reference_recursion(batch):
-    """costate_option = 1 at the generic set against _pmp_reference (test_gpu_parity.py) on the oracle's derivatives
+    """costate_option = 1 at the generic set against parity_ref.pmp_reference on the oracle's derivatives
     with the same parameters, 8 samples, 1e-11: the recursion's dc/dx carries the goal-attitude gradient (wqf) and its
     A_k^T the az terms."""
     eng = engine()
@@ -298,9 +298,9 @@ def test_pmp_costates_match_reference_recursion(batch):
     # the goal-attitude gradient is part of what is compared: the recursion without it is another vector
     far = 0.0
     for b in range(B):
-        ref = _pmp_reference(x[b], u[b], prob["goal"][b], prob["p"][b], prob["q"][b], params=oracle_params())
+        ref = pmp_reference(x[b], u[b], prob["goal"][b], prob["p"][b], prob["q"][b], params=oracle_params())
         assert np.max(np.abs(lam[b] - ref) / (1.0 + np.abs(ref))) < 1e-11, b
-        no_q = _pmp_reference(x[b], u[b], prob["goal"][b], prob["p"][b], prob["q"][b], params=oracle_params(wqf=0.0))
+        no_q = pmp_reference(x[b], u[b], prob["goal"][b], prob["p"][b], prob["q"][b], params=oracle_params(wqf=0.0))
         far = max(far, float(np.max(np.abs(no_q - ref) / (1.0 + np.abs(ref)))))
     print(f"PMP costates: the recursion without the wqf gradient differs by up to {far:.3e}")
     assert far > 1e-3

@@ -1,7 +1,7 @@
 """lafse3_ocp_sensitivity_ex (csrc/sens.inc) at the generic parameter set (generic_params.py): dt,
 mass, arm_l, c_tau, grav, wthrust, du_weight, tra_w_peak and tra_w_decay enter the products dtm, bwx..bwz and dwk of the
 sensitivity right-hand sides, and an error that cancels at the reference's constants is invisible to
-test_gpu_sens.py / test_gpu_sens_ex.py.  Rules, constants and checking functions are those two files'.
+test_gpu_sens.py / test_gpu_sens_ex.py.  Rules, constants and checking functions are theirs (sens_yardstick.py).
 
 Run on an MI355X:  python -m pytest tests/test_gpu_generic_sens.py -m gpu -q -s
 
@@ -31,13 +31,12 @@ torch = pytest.importorskip("torch")
 
 import generic_params as GP  # noqa: E402
 import newton_cases as NC  # noqa: E402
-import test_gpu_sens as TS  # noqa: E402
-import test_gpu_sens_ex as TX  # noqa: E402
+import sens_yardstick as Y  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 GENERIC = GP.GENERIC
-H, ADMIT, F = TX.H, TX.ADMIT, TX.F
+SL3 = {g: Y.SL[g] for g in ("theta", "ini", "goal")}
 N_THETA, N_INI = 8, 4
 _runs = {}
 
@@ -50,15 +49,14 @@ def batch():
 
 def gpu_run(batch, horizon):
     """One ocp_sensitivity_ex launch with all three groups on 8 samples of the horizon (shared, never modified)."""
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
+    Y.require_gpu()
     if horizon not in _runs:
         from learningagileflight_se3_amd.engine import Engine
         e = Engine(horizon=horizon, **GENERIC.fields())
         prob = GP.problem(batch, horizon, range(N_THETA))
         args = (prob["ini"], prob["goal"], prob["p"], prob["a"], prob["t"])
-        g = TX._np(e.ocp_sensitivity_ex(*args, u_last=prob["ulast"], want=("x", "u", "dx", "du", "gain")))
-        old = TX._np(e.ocp_sensitivity(*args, u_last=prob["ulast"]))
+        g = Y.to_numpy(e.ocp_sensitivity_ex(*args, u_last=prob["ulast"], want=("x", "u", "dx", "du", "gain")))
+        old = Y.to_numpy(e.ocp_sensitivity(*args, u_last=prob["ulast"]))
         torch.cuda.synchronize()
         e.check_device()
         _runs[horizon] = (prob, g, old)
@@ -66,28 +64,8 @@ def gpu_run(batch, horizon):
 
 
 def oracle_fd(prob, n, horizon, cols):
-    """Central differences of the oracle's solve at the generic set, steps H and 2 H, for the first n samples of
-    `prob` and the parameter columns `cols` of z = (p_tra 3, a_tra 3, t, ini_state 13, goal 3), one batched call.
-    Returns J_h (n, Q, E), e, admitted, scale (n, Q) as test_gpu_sens.oracle_fd does."""
-    from oracle import oracle as O
-    z0 = np.concatenate([prob["p"][:n], prob["a"][:n], prob["t"][:n, None], prob["ini"][:n], prob["goal"][:n]], axis=1)
-    steps = [(q, s * m * H) for q in cols for m in (1, 2) for s in (+1, -1)]
-    Z = np.repeat(z0[None], len(steps), 0)                                      # (steps, n, 23)
-    for j, (q, d) in enumerate(steps):
-        Z[j, :, q] += d
-    Z = Z.reshape(-1, 23)
-    quat = np.stack([O.rd2quat(a) for a in Z[:, 3:6]])
-    ul = np.tile(prob["ulast"][:n], (len(steps), 1))
-    r = O.solve(np.ascontiguousarray(Z[:, 7:20]), np.ascontiguousarray(Z[:, 20:23]), np.ascontiguousarray(Z[:, 0:3]),
-                quat, np.ascontiguousarray(Z[:, 6]), ulast=ul, params=NC.oracle_params(GENERIC, horizon=horizon))
-    Q = len(cols)
-    z = TS._traj(r["x"], r["u"]).reshape(Q, 2, 2, n, -1)                        # [q][h, 2h][+, -][sample]
-    ok = (r["status"] <= 1).reshape(Q, 2, 2, n).all(axis=(1, 2)).T
-    J_h = np.transpose((z[:, 0, 0] - z[:, 0, 1]) / (2 * H), (1, 0, 2))
-    J_2h = np.transpose((z[:, 1, 0] - z[:, 1, 1]) / (4 * H), (1, 0, 2))
-    scale = np.abs(J_h).max(-1)
-    e = np.abs(J_h - J_2h).max(-1) / scale
-    return {"J": J_h, "e": e, "admitted": ok & (e <= ADMIT), "scale": scale}
+    """sens_yardstick.oracle_fd with the oracle at the generic set; u_last is the problem's."""
+    return Y.oracle_fd(prob, n, horizon, cols, NC.oracle_params(GENERIC, horizon=horizon))
 
 
 @pytest.mark.parametrize("horizon", [20, 7])
@@ -96,8 +74,8 @@ def test_theta_columns_against_oracle_finite_differences(batch, horizon):
     fd = oracle_fd(prob, N_THETA, horizon, range(0, 7))
     assert np.all(g["status"] <= 1) and np.all(g["sens_status"] != 1)
     assert g["dx"].shape == (N_THETA, 23, horizon + 1, 13) and g["du"].shape == (N_THETA, 23, horizon, 4)
-    TS._check_against_fd(TS._traj(g["dx"][:, :7], g["du"][:, :7]), g["sens_status"], fd,
-                         f"generic set, horizon {horizon}, theta")
+    Y.check_against_fd(Y.traj(g["dx"][:, :7], g["du"][:, :7]), g["sens_status"], fd,
+                       f"generic set, horizon {horizon}, theta", Y.F)
 
 
 @pytest.mark.parametrize("horizon", [20, 7])
@@ -105,8 +83,10 @@ def test_ini_and_goal_columns_against_oracle_finite_differences(batch, horizon):
     prob, g, _ = gpu_run(batch, horizon)
     n = N_INI
     fd = oracle_fd(prob, n, horizon, range(7, 23))
-    TX._check_against_fd(TS._traj(g["dx"][:n, 7:], g["du"][:n, 7:]), g["sens_status"][:n], fd,
-                         f"generic set, horizon {horizon}, ini + goal")
+    label = f"generic set, horizon {horizon}, ini + goal"
+    ini, goal = fd["admitted"][:, :13], fd["admitted"][:, 13:]
+    print(f"{label}: oracle admits ini {int(ini.sum())} of {ini.size}, goal {int(goal.sum())} of {goal.size}")
+    Y.check_against_fd(Y.traj(g["dx"][:n, 7:], g["du"][:n, 7:]), g["sens_status"][:n], fd, label, Y.F)
 
 
 @pytest.mark.parametrize("horizon", [20, 7, 2, 1])
@@ -114,8 +94,8 @@ def test_adjoint_gain_equals_forward_du0(batch, horizon):
     _, g, _ = gpu_run(batch, horizon)
     assert g["gain"].shape == (N_THETA, 4, 23)
     assert np.all(np.isfinite(g["du"])) and np.all(np.isfinite(g["gain"]))
-    assert TX.ADJ_BAR <= 1e-5
-    assert TX._adjoint_difference(g, f"generic set, horizon {horizon}") <= TX.ADJ_BAR
+    assert Y.ADJ_BAR <= 1e-5
+    assert Y.adjoint_difference(g, f"generic set, horizon {horizon}", SL3, Y.ADJ_BAR) <= Y.ADJ_BAR
 
 
 @pytest.mark.parametrize("horizon", [20, 7, 2, 1])

@@ -18,6 +18,8 @@ import yardstick
 
 torch = pytest.importorskip("torch")
 
+from parity_ref import grad_parity, pmp_reference  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
@@ -381,22 +383,6 @@ def test_dropin_run_quad_and_ocsys(eng, batch):
     assert np.max(np.abs(u0 - ref["u"][0, 0])) < 1e-6
 
 
-def _pmp_reference(x, u, goal, p, q, params=None):
-    """quad_OC.py:188-201 restated on the oracle's model / cost derivatives: lam_{N-1} = dh/dx(x_N),
-    lam_{k-1} = dc/dx(x_k) + A_k^T lam_k, c = h = the goal cost (quad_model.py:185-196, wk = 0).  params: the
-    oracle's parameter block (None: the defaults)."""
-    from oracle import oracle as O
-    N = u.shape[0]
-    _, A, _, _, _ = O.model_eval(x[:N], u, np.zeros((N, 13)), params=params)
-    _, _, g, _ = O.cost_eval(x, np.repeat(goal[None], N + 1, 0), np.repeat(p[None], N + 1, 0),
-                             np.repeat(q[None], N + 1, 0), 0.0, params=params)
-    lam = np.zeros((N, 13))
-    lam[N - 1] = g[N]
-    for k in range(N - 1, 0, -1):
-        lam[k - 1] = g[k] + A[k].T @ lam[k]
-    return lam
-
-
 def test_pmp_costates_match_reference_recursion(eng, batch):
     """costate_option=1 (quad_OC.py:188-201): the GPU recursion on the GPU optimum equals the reference's
     recursion evaluated with the oracle's Jacobians on the same trajectory; x, u are unchanged."""
@@ -412,7 +398,7 @@ def test_pmp_costates_match_reference_recursion(eng, batch):
     x, u, lam = (o1[k].cpu().numpy() for k in ("x", "u", "lam"))
     assert np.array_equal(x, o0["x"].cpu().numpy()) and np.array_equal(u, o0["u"].cpu().numpy())
     for b in range(B):
-        ref = _pmp_reference(x[b], u[b], sb["goal"][b], p[b], O.rd2quat(a[b]))
+        ref = pmp_reference(x[b], u[b], sb["goal"][b], p[b], O.rd2quat(a[b]))
         assert np.max(np.abs(lam[b] - ref) / (1.0 + np.abs(ref))) < 1e-11, b
     # OCSys mirror passes the option through
     from learningagileflight_se3_amd.quad_policy import OCSys
@@ -484,34 +470,11 @@ def test_fp32_twin_full_size(eng):
         assert np.array_equal(r32[k].cpu().numpy(), r64[k].cpu().numpy().astype(np.float32)), k
 
 
-def _grad_parity(o8, s9, it9, args, label, params=None):
-    """sol_gradient rows against the oracle (9 solves each) with the north_star bound: >= 95 % of the samples
-    whose 18 solves converged agree within 1e-5 relative, and all of them within 1e-4.  Every sample at or
-    above 1e-5 is listed with its per-solve iteration-count difference (GPU - oracle): a nonzero difference
-    means the two IPMs took another accept/reject decision at IPOPT's 1e-8 tolerance on that solve.  params: the
-    oracle's parameter block (None: the defaults)."""
-    from oracle import oracle as O
-    rit = np.zeros(it9.shape, np.int32)
-    r8, rR, rS = O.sol_gradient(*args, iters=rit, params=params)
-    ok = (s9 <= 1).all(1) & (rS <= 1).all(1)
-    per = (np.abs(o8[:, :7] - r8[:, :7]) / (1.0 + np.abs(r8[:, :7]))).max(1)
-    same = (it9 == rit).all(1)
-    outl = [(int(i), float(per[i]), (it9[i] - rit[i]).tolist()) for i in np.nonzero(ok & (per >= 1e-5))[0]]
-    stats = dict(n=len(per), converged=int(ok.sum()), same_path=int(same.sum()),
-                 within_1e5=float(np.mean(per[ok] < 1e-5)), max=float(per[ok].max()),
-                 max_same_path=float(per[ok & same].max()) if (ok & same).any() else None)
-    print(f"{label}: {stats}; outliers (sample, rel diff, iteration difference per solve): {outl}")
-    assert ok.mean() >= 0.9, stats
-    # north_star: every converged sample within 1e-5 relative
-    assert stats["max"] < 1e-5, (stats, outl)
-    return stats, outl
-
-
 def test_configs3_shard_8192_samples(eng):
     """configs[3]'s per-GPU shard (65 536 episodes / 8 GPUs = 8 192 samples = 73 728 NLP solves) in one launch:
     every out8 finite, >= 99 % of the solves solved/acceptable, the seeded 64-sample subset re-solved alone
     reproduces its rows of the full launch bit for bit (no dependence on batch position or size), and the subset
-    against the CPU oracle under _grad_parity's bound (north_star: <= 1e-5 relative)."""
+    against the CPU oracle under grad_parity's bound (north_star: <= 1e-5 relative)."""
     from learningagileflight_se3_amd import scenario as S
     sb = S.synthetic_batch(8192, seed=3)
     args = (sb["ini"], sb["goal"], sb["gate12"], sb["dnn_out"])
@@ -530,14 +493,14 @@ def test_configs3_shard_8192_samples(eng):
     sub = tuple(a[idx] for a in args)
     alone = eng.sol_gradient(*sub).cpu().numpy()
     assert np.array_equal(alone, o8[idx])
-    _grad_parity(o8[idx], s9[idx], it[idx], sub, "configs[3] shard subset")
+    grad_parity(o8[idx], s9[idx], it[idx], sub, "configs[3] shard subset")
 
 
 def test_last_inputs_scenario(eng, golden):
     """The scenario the reference ships in gym_pybullet_drone/last_inputs.npy (start, goal, yaw, gate width and
     pitch) through the GPU sol_gradient and get_input, against the oracle, with the trained DNN2's outputs
     on that scenario (moving.npz episode 0, nn3_1.pth; 12 from the episode + 52 on perturbed inputs) as the
-    traversal parameters, under _grad_parity's bound."""
+    traversal parameters, under grad_parity's bound."""
     from learningagileflight_se3_amd import scenario as S
     from oracle import oracle as O
     s = golden("last_inputs")["inputs"]
@@ -569,7 +532,7 @@ def test_last_inputs_scenario(eng, golden):
     r8, rR, rS = O.sol_gradient(ini, goal, gate12, outs)
     assert np.array_equal(S9 <= 1, rS <= 1) and np.mean(S9 <= 1) >= 0.9
     ok = (S9 <= 1).all(1) & (rS <= 1).all(1)
-    _grad_parity(o8, S9, it, (ini, goal, gate12, outs), "last_inputs scenario (64 DNN2 outputs)")
+    grad_parity(o8, S9, it, (ini, goal, gate12, outs), "last_inputs scenario (64 DNN2 outputs)")
     assert np.max(np.abs(o8[ok, 7] - r8[ok, 7]) / np.abs(r8[ok, 7])) < 1e-6
     # get_input on the scenario's initial state (float32 DNN outputs, t unrounded; quad_policy.py:202-211)
     u0, _ = eng.get_input(ini[:1], goal[:1], outs[:1])

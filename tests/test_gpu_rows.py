@@ -62,7 +62,7 @@ def test_rl_loop_rewards_match_oracle(eng):
         gate12 = scenario.gate_corners(samples[:, 7], samples[:, 8])
         r8, _, rs = O.sol_gradient(ini, samples[:, 3:6], gate12, out)
         assert np.all(rs <= 1)
-        # north_star: 1e-5 relative (gradients on the (1 + |g|) scale of _grad_parity)
+        # north_star: 1e-5 relative (gradients on the (1 + |g|) scale of parity_ref.grad_parity)
         assert np.max(np.abs(g[:, 7] - r8[:, 7]) / np.maximum(1.0, np.abs(r8[:, 7]))) < 1e-5
         assert np.max(np.abs(g[:, :7] - r8[:, :7]) / (1.0 + np.abs(r8[:, :7]))) < 1e-5
 
@@ -73,7 +73,7 @@ def test_moving_gate_receding_horizon_matches_reference_loop(eng, golden):
     oracle in place of ocSolver; DNN2 evaluated per sample on the CPU as the reference does, so the only
     differences are the NLP solves (GPU get_input vs oracle) and their propagation through the plant."""
     from learningagileflight_se3_amd import moving_gate as MG
-    from test_moving_host import dnn2_from_fixture, fixture_episodes, per_sample
+    from moving_cases import dnn2_from_fixture, fixture_episodes, per_sample
     g = golden("moving")
     n_ep, steps = g["t"].shape
     samples, noise = fixture_episodes(g)
@@ -93,7 +93,7 @@ def test_moving_gate_full_length_episode(eng, golden):
     evaluates it, so the differences are the NLP solves (GPU get_input vs oracle, agreeing to IPOPT's tolerance)
     and their propagation through the closed loop."""
     from learningagileflight_se3_amd import moving_gate as MG
-    from test_moving_host import dnn2_from_fixture, fixture_episodes, per_sample
+    from moving_cases import dnn2_from_fixture, fixture_episodes, per_sample
     g = golden("moving500")
     n_ep, steps = g["t"].shape
     assert (n_ep, steps) == (1, 500) and g["source"][0] == 0
@@ -114,7 +114,7 @@ def test_traversal_time_kernel_matches_reference_loop_t(eng, golden):
     test |t2 - t1| <= 0.001 is discontinuous: an fp32 rounding difference between the kernel's DNN2 and torch's can
     end the halving updates one step earlier or later, moving t by at most half the last update (<= 5e-4).
     Required: >= 98 % of the steps within 1e-5 of the reference, every step within 5e-4 + 1e-5."""
-    from test_moving_host import dnn2_from_fixture
+    from moving_cases import dnn2_from_fixture
     g = golden("moving")
     net = dnn2_from_fixture(golden("dnn2_nn3_1")).cuda()
     n_ep, steps = g["t"].shape
@@ -156,7 +156,7 @@ def test_traversal_time_kernel_matches_torch_fixed_point(eng, golden):
     rounding of the network's output (carried through the halving updates), not bit for bit."""
     from learningagileflight_se3_amd import moving_gate as MG
     from learningagileflight_se3_amd import scenario as S
-    from test_moving_host import dnn2_from_fixture
+    from moving_cases import dnn2_from_fixture
     net = dnn2_from_fixture(golden("dnn2_nn3_1")).cuda()
     rs = np.random.RandomState(91)
     samples = np.stack([S.nn_sample(rs) for _ in range(64)])

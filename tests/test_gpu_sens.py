@@ -30,64 +30,30 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import sens_yardstick as Y  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-H = 1e-4             # finite-difference step of the oracle yardstick (and 2 H)
-ADMIT = 1e-3         # admission: h-versus-2h disagreement relative to max|J_h|
-F_MEASURED = 3.914e-4   # largest err - 10 e over the admitted pairs of the first GPU run (horizon 50 and 20)
-F = 1e-3                # F_MEASURED rounded up to the next power of ten (<= ADMIT)
+F = Y.F              # the bound's F, measured on this file's first GPU run (module docstring)
 NS = 16              # samples of the finite-difference comparison
+THETA = range(0, 7)  # the columns of sens_yardstick.oracle_fd's z that are theta
 
 
 @pytest.fixture(scope="module")
 def eng():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
+    Y.require_gpu()
     from learningagileflight_se3_amd.engine import Engine
     return Engine()
 
 
 @pytest.fixture(scope="module")
 def batch():
-    from learningagileflight_se3_amd import scenario as S
-    sb = S.synthetic_batch(64, seed=2025)
-    sb["p"] = sb["dnn_out"][:, :3].astype(np.float64)
-    sb["a"] = sb["dnn_out"][:, 3:6].astype(np.float64)
-    sb["t"] = sb["dnn_out"][:, 6].astype(np.float64)
-    return sb
-
-
-def _traj(x, u):
-    """(B, ..., N+1, 13), (B, ..., N, 4) -> (B, ..., 13 (N+1) + 4 N): the trajectory entries of one solve."""
-    return np.concatenate([x.reshape(*x.shape[:-2], -1), u.reshape(*u.shape[:-2], -1)], axis=-1)
-
-
-def oracle_fd(sb, n, horizon=50, t=None):
-    """Central differences of oracle.solve at H and 2 H for the first n samples and the 7 parameters, one batched
-    oracle call.  Returns J_h (n, 7, E), e (n, 7), admitted (n, 7), scale = max|J_h| (n, 7)."""
-    from oracle import oracle as O
-    prm = O.default_params(horizon=horizon)
-    th = np.concatenate([sb["p"][:n], sb["a"][:n], (sb["t"][:n] if t is None else t)[:, None]], axis=1)   # (n, 7)
-    steps = [(q, s * m * H) for q in range(7) for m in (1, 2) for s in (+1, -1)]
-    TH = np.repeat(th[None], len(steps), 0)                                    # (28, n, 7)
-    for j, (q, d) in enumerate(steps):
-        TH[j, :, q] += d
-    TH = TH.reshape(-1, 7)
-    quat = np.stack([O.rd2quat(a) for a in TH[:, 3:6]])
-    rep = lambda v: np.tile(v[:n], (len(steps), 1))
-    r = O.solve(rep(sb["ini"]), rep(sb["goal"]), TH[:, :3], quat, TH[:, 6], params=prm)
-    z = _traj(r["x"], r["u"]).reshape(7, 2, 2, n, -1)                          # [q][h, 2h][+, -][sample]
-    ok = (r["status"] <= 1).reshape(7, 2, 2, n).all(axis=(1, 2)).T             # (n, 7)
-    J_h = np.transpose((z[:, 0, 0] - z[:, 0, 1]) / (2 * H), (1, 0, 2))         # (n, 7, E)
-    J_2h = np.transpose((z[:, 1, 0] - z[:, 1, 1]) / (4 * H), (1, 0, 2))
-    scale = np.abs(J_h).max(-1)
-    e = np.abs(J_h - J_2h).max(-1) / scale
-    return {"J": J_h, "e": e, "admitted": ok & (e <= ADMIT), "scale": scale}
+    return Y.batch()
 
 
 @pytest.fixture(scope="module")
 def fd16(batch):
-    return oracle_fd(batch, NS)
+    return Y.oracle_fd(batch, NS, 50, THETA)
 
 
 @pytest.fixture(scope="module")
@@ -96,24 +62,7 @@ def sens64(eng, batch):
     sb = batch
     out = eng.ocp_sensitivity(sb["ini"], sb["goal"], sb["p"], sb["a"], sb["t"], want=("x", "u", "lam", "cost", "dx", "du"))
     torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def _check_against_fd(J_gpu, sens_status, fd, label, max_left_out=0.15):
-    """err <= 10 e + F on the admitted pairs of instances with sens_status 0; prints every figure first."""
-    adm = fd["admitted"]
-    print(f"{label}: oracle admits {int(adm.sum())} of {adm.size} pairs; sens_status histogram "
-          f"{np.bincount(sens_status, minlength=3).tolist()}")
-    assert (~adm).mean() <= max_left_out, f"{label}: {int((~adm).sum())} of {adm.size} pairs not admitted"
-    use = adm & (sens_status == 0)[:, None]
-    err = np.abs(J_gpu - fd["J"]).max(-1) / fd["scale"]
-    excess = np.where(use, err - 10 * fd["e"], -np.inf)
-    i, q = np.unravel_index(np.argmax(excess), excess.shape)
-    print(f"{label}: {int(use.sum())} pairs compared; max err {err[use].max():.3e}; max(err - 10 e) {excess.max():.3e} "
-          f"at sample {i} parameter {q} (err {err[i, q]:.3e}, e {fd['e'][i, q]:.3e}); median err {np.median(err[use]):.3e}")
-    assert use.sum() >= adm.sum() - 7                     # at most one instance without a sensitivity
-    assert excess.max() <= F, (label, float(excess.max()), int(i), int(q))
-    return err
+    return Y.to_numpy(out)
 
 
 def test_outputs_are_the_plain_solves_bit_for_bit(eng, batch, sens64):
@@ -149,7 +98,7 @@ def test_against_oracle_finite_differences(sens64, fd16):
     st = sens64["sens_status"][:NS]
     assert np.sum(st == 2) <= 1, st
     assert np.all(sens64["status"][:NS] <= 1) and np.all(st != 1)
-    _check_against_fd(_traj(sens64["dx"][:NS], sens64["du"][:NS]), st, fd16, "horizon 50")
+    Y.check_against_fd(Y.traj(sens64["dx"][:NS], sens64["du"][:NS]), st, fd16, "horizon 50", F)
 
 
 def test_short_horizon(batch):
@@ -162,14 +111,14 @@ def test_short_horizon(batch):
     e = Engine(horizon=20)
     n = 4
     t = sb["t"][:n]
-    fd = oracle_fd(sb, n, horizon=20)
+    fd = Y.oracle_fd(sb, n, 20, THETA)
     out = e.ocp_sensitivity(sb["ini"][:n], sb["goal"][:n], sb["p"][:n], sb["a"][:n], t)
     g = {k: v.cpu().numpy() for k, v in out.items()}
     assert g["dx"].shape == (n, 7, 21, 13) and g["du"].shape == (n, 7, 20, 4)
     assert np.all(g["dx"][:, :, 0, :] == 0.0)
     ref = e.ocp_solve(sb["ini"][:n], sb["goal"][:n], sb["p"][:n], sb["a"][:n], t)
     assert np.array_equal(g["x"], ref["x"].cpu().numpy()) and np.array_equal(g["u"], ref["u"].cpu().numpy())
-    _check_against_fd(_traj(g["dx"], g["du"]), g["sens_status"], fd, "horizon 20", max_left_out=7 / 28)
+    Y.check_against_fd(Y.traj(g["dx"], g["du"]), g["sens_status"], fd, "horizon 20", F, max_left_out=7 / 28)
     one = e.ocp_sensitivity(sb["ini"][:1], sb["goal"][:1], sb["p"][:1], sb["a"][:1], t[:1])
     assert one["dx"].shape == (1, 7, 21, 13) and one["du"].shape == (1, 7, 20, 4)
     assert int(one["status"][0]) <= 1 and int(one["sens_status"][0]) == int(g["sens_status"][0])
@@ -252,7 +201,7 @@ def test_autograd_through_mpc_layer(eng, batch, sens64, fd16):
     assert rel.max() <= 1e-12
     # against the oracle's finite difference of L on the admitted pairs: |sum W (J_gpu - J_h)| <= sum|W| max|J_gpu -
     # J_h| <= sum|W| (10 e + F) max|J_h| (Hoelder), plus the float32 rounding of the returned gradient
-    W = _traj(W_x, W_u)                                                       # (n, E)
+    W = Y.traj(W_x, W_u)                                                      # (n, E)
     L_fd = np.einsum("bqe,be->bq", fd16["J"], W)
     use = fd16["admitted"] & (sens64["sens_status"][:n] == 0)[:, None]
     bound = np.abs(W).sum(-1)[:, None] * (10 * fd16["e"] + F) * fd16["scale"] + 2.0 ** -23 * np.abs(L_fd)

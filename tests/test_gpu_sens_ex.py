@@ -37,45 +37,37 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import sens_yardstick as Y  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-H = 1e-4             # finite-difference step of the oracle yardstick (and 2 H)
-ADMIT = 1e-3         # admission: h-versus-2h disagreement relative to max|J_h|
-F = 1e-3             # tests/test_gpu_sens.py's F (= ADMIT)
+F = Y.F              # tests/test_gpu_sens.py's F (= ADMIT)
 # largest err - 10 e per horizon on the first GPU run (admitted pairs with sens_status 0)
 MEASURED = {50: 3.866e-05, 20: 7.800e-06, 2: 7.572e-12}
 ADJ_MEASURED = 1.600e-07   # largest |gain - du_0| / group scale on the first GPU run (horizons 50, 20, 2, 1)
-ADJ_BAR = 1e-6       # ADJ_MEASURED rounded up to the next power of ten, at most 1e-5
+ADJ_BAR = Y.ADJ_BAR  # ADJ_MEASURED rounded up to the next power of ten, at most 1e-5
 NFD = 8              # samples of the horizon-50 finite-difference comparison
 NS = 16              # samples of the shared horizon-50 launch
+_np = Y.to_numpy
 GROUPS = ("theta", "ini", "goal")
-SL = {"theta": slice(0, 7), "ini": slice(7, 20), "goal": slice(20, 23)}
+SL = {g: Y.SL[g] for g in GROUPS}
+INI_GOAL = range(7, 23)                  # the ini_state and goal columns of sens_yardstick.oracle_fd's z
 
 
 @pytest.fixture(scope="module")
 def eng():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
+    Y.require_gpu()
     from learningagileflight_se3_amd.engine import Engine
     return Engine()
 
 
 @pytest.fixture(scope="module")
 def batch():
-    from learningagileflight_se3_amd import scenario as S
-    sb = S.synthetic_batch(64, seed=2025)
-    sb["p"] = sb["dnn_out"][:, :3].astype(np.float64)
-    sb["a"] = sb["dnn_out"][:, 3:6].astype(np.float64)
-    sb["t"] = sb["dnn_out"][:, 6].astype(np.float64)
-    return sb
+    return Y.batch()
 
 
 def _args(sb, n):
     return tuple(sb[k][:n] for k in ("ini", "goal", "p", "a", "t"))
-
-
-def _np(out):
-    return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
 
 
 @pytest.fixture(scope="module")
@@ -86,59 +78,19 @@ def full16(eng, batch):
     return _np(out)
 
 
-def _traj(x, u):
-    return np.concatenate([x.reshape(*x.shape[:-2], -1), u.reshape(*u.shape[:-2], -1)], axis=-1)
-
-
-def oracle_fd(sb, n, horizon, with_goal=True):
-    """Central differences of oracle.solve at H and 2 H for the first n samples and the 13 ini_state (+ 3 goal)
-    parameters, one batched oracle call.  Returns J_h (n, Q, E), e, admitted, scale = max|J_h| (n, Q)."""
-    from oracle import oracle as O
-    prm = O.default_params(horizon=horizon)
-    Q = 16 if with_goal else 13
-    z0 = np.concatenate([sb["ini"][:n], sb["goal"][:n]], axis=1)                # (n, 16)
-    steps = [(q, s * m * H) for q in range(Q) for m in (1, 2) for s in (+1, -1)]
-    Z = np.repeat(z0[None], len(steps), 0)
-    for j, (q, d) in enumerate(steps):
-        Z[j, :, q] += d
-    Z = Z.reshape(-1, 16)
-    rep = lambda v: np.tile(v[:n], (len(steps),) + (1,) * (v.ndim - 1))
-    quat = np.stack([O.rd2quat(a) for a in sb["a"][:n]])
-    r = O.solve(np.ascontiguousarray(Z[:, :13]), np.ascontiguousarray(Z[:, 13:]), rep(sb["p"]), rep(quat),
-                rep(sb["t"]), params=prm)
-    z = _traj(r["x"], r["u"]).reshape(Q, 2, 2, n, -1)                           # [q][h, 2h][+, -][sample]
-    ok = (r["status"] <= 1).reshape(Q, 2, 2, n).all(axis=(1, 2)).T              # (n, Q)
-    J_h = np.transpose((z[:, 0, 0] - z[:, 0, 1]) / (2 * H), (1, 0, 2))
-    J_2h = np.transpose((z[:, 1, 0] - z[:, 1, 1]) / (4 * H), (1, 0, 2))
-    scale = np.abs(J_h).max(-1)
-    e = np.abs(J_h - J_2h).max(-1) / scale
-    return {"J": J_h, "e": e, "admitted": ok & (e <= ADMIT), "scale": scale}
-
-
-def _check_against_fd(J_gpu, sens_status, fd, label):
-    """err <= 10 e + F on the admitted pairs of instances with sens_status 0; prints every figure first."""
-    adm = fd["admitted"]
-    print(f"{label}: oracle admits {int(adm.sum())} of {adm.size} pairs (ini {int(adm[:, :13].sum())} of "
-          f"{adm[:, :13].size}, goal {int(adm[:, 13:].sum())} of {adm[:, 13:].size}); sens_status histogram "
-          f"{np.bincount(sens_status, minlength=3).tolist()}")
-    use = adm & (sens_status == 0)[:, None]
-    err = np.abs(J_gpu - fd["J"]).max(-1) / fd["scale"]
-    excess = np.where(use, err - 10 * fd["e"], -np.inf)
-    i, q = np.unravel_index(np.argmax(excess), excess.shape)
-    print(f"{label}: {int(use.sum())} pairs compared; max err {err[use].max():.3e}; max(err - 10 e) {excess.max():.3e} "
-          f"at sample {i} parameter {q} (err {err[i, q]:.3e}, e {fd['e'][i, q]:.3e}); median err {np.median(err[use]):.3e}")
-    assert (~adm).mean() <= 0.15, f"{label}: {int((~adm).sum())} of {adm.size} pairs not admitted"
-    assert use.sum() >= adm.sum() - adm.shape[1]          # at most one instance without a sensitivity
-    assert excess.max() <= F, (label, float(excess.max()), int(i), int(q))
-
-
 # ---- (a) forward columns against the oracle's finite differences ---------------------------------------------
 
+def _check_against_fd(J_gpu, sens_status, fd, label):
+    ini, goal = fd["admitted"][:, :13], fd["admitted"][:, 13:]
+    print(f"{label}: oracle admits ini {int(ini.sum())} of {ini.size}, goal {int(goal.sum())} of {goal.size}")
+    Y.check_against_fd(J_gpu, sens_status, fd, label, F)
+
+
 def test_forward_columns_against_oracle_finite_differences_horizon_50(batch, full16):
-    fd = oracle_fd(batch, NFD, 50)
+    fd = Y.oracle_fd(batch, NFD, 50, INI_GOAL)
     st = full16["sens_status"][:NFD]
     assert np.all(full16["status"][:NFD] <= 1) and np.all(st != 1)
-    J = _traj(full16["dx"][:NFD, 7:], full16["du"][:NFD, 7:])
+    J = Y.traj(full16["dx"][:NFD, 7:], full16["du"][:NFD, 7:])
     _check_against_fd(J, st, fd, "horizon 50")
 
 
@@ -147,39 +99,17 @@ def test_forward_columns_against_oracle_finite_differences_short(batch, horizon)
     from learningagileflight_se3_amd.engine import Engine
     n = 4
     e = Engine(horizon=horizon)
-    fd = oracle_fd(batch, n, horizon, with_goal=horizon != 2)
+    fd = Y.oracle_fd(batch, n, horizon, INI_GOAL if horizon != 2 else range(7, 20))
     g = _np(e.ocp_sensitivity_ex(*_args(batch, n), groups=("ini", "goal"), want=("x", "u", "dx", "du")))
     assert g["dx"].shape == (n, 16, horizon + 1, 13) and g["du"].shape == (n, 16, horizon, 4)
     Q = fd["J"].shape[1]
-    _check_against_fd(_traj(g["dx"][:, :Q], g["du"][:, :Q]), g["sens_status"], fd, f"horizon {horizon}")
+    _check_against_fd(Y.traj(g["dx"][:, :Q], g["du"][:, :Q]), g["sens_status"], fd, f"horizon {horizon}")
 
 
 # ---- (b) adjoint against forward ------------------------------------------------------------------------------
 
-def _adjoint_difference(g, label):
-    """max over live instances, groups and entries of |gain[b, a, q] - du[b, q, 0, a]| / max|du[b, group, 0, :]|."""
-    live = g["sens_status"] == 0
-    du0 = np.transpose(g["du"][:, :, 0, :], (0, 2, 1))                         # (B, 4, P)
-    assert g["gain"].shape == du0.shape
-    worst, where = 0.0, None
-    for name, sl in SL.items():
-        diff = np.abs(g["gain"][:, :, sl] - du0[:, :, sl]).max(axis=(1, 2))
-        scale = np.abs(du0[:, :, sl]).max(axis=(1, 2))
-        # a group that does not move u_0 at all (theta at horizon 1: no traversal stage) must give exact zeros
-        rel = np.where(scale > 0, diff / np.where(scale > 0, scale, 1.0), np.where(diff == 0, 0.0, np.inf))
-        rel = np.where(live, rel, 0.0)
-        b = int(np.argmax(rel))
-        print(f"{label}: group {name}: max relative |gain - du_0| {rel.max():.3e} (sample {b}, scale {scale[b]:.3e})")
-        if rel.max() >= worst:
-            worst, where = float(rel.max()), (name, b)
-    print(f"{label}: {int(live.sum())} of {live.size} instances live; max relative difference {worst:.3e} at {where} "
-          f"(bar {ADJ_BAR:.0e})")
-    assert live.sum() >= live.size - 1
-    return worst
-
-
 def test_adjoint_gain_equals_forward_du0_horizon_50(eng, batch, full16):
-    assert _adjoint_difference(full16, "horizon 50") <= ADJ_BAR
+    assert Y.adjoint_difference(full16, "horizon 50", SL, ADJ_BAR) <= ADJ_BAR
     # a gain-only call (dx = du = NULL) returns the same gain bit for bit
     only = _np(eng.ocp_sensitivity_ex(*_args(batch, NS), want=("gain",)))
     assert set(only) == {"gain", "status", "iters", "sens_status", "columns"}
@@ -195,7 +125,7 @@ def test_adjoint_gain_equals_forward_du0_short(batch, horizon):
     g = _np(e.ocp_sensitivity_ex(*_args(batch, n), want=("du", "gain")))
     assert g["du"].shape == (n, 23, horizon, 4) and g["gain"].shape == (n, 4, 23)
     assert np.all(np.isfinite(g["du"])) and np.all(np.isfinite(g["gain"]))
-    assert _adjoint_difference(g, f"horizon {horizon}") <= ADJ_BAR
+    assert Y.adjoint_difference(g, f"horizon {horizon}", SL, ADJ_BAR) <= ADJ_BAR
     only = _np(e.ocp_sensitivity_ex(*_args(batch, n), want=("gain",)))
     assert np.array_equal(only["gain"], g["gain"])
 

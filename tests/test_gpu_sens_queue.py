@@ -33,7 +33,7 @@ Per entry point, on the device (torch.equal on the bit patterns of index-selecte
     unpoisoned instances status <= 1;
  5. Engine.check_device() passes;
  6. on the subset, ocp_vjp's grad equals dx, du of a horizon-50 ocp_sensitivity_w launch of the subset contracted with
-    g_x, g_u (standard normal, np.random.default_rng(7)) under test_gpu_vjp.ADJ_BAR on that module's scale.
+    g_x, g_u (standard normal, np.random.default_rng(7)) under sens_yardstick.VJP_BAR on vjp_relative's scale.
 First GPU run (256 CUs: slots 1024, B 2304; 330 non-finite instances, for ocp_vjp also 329 records of another horizon
 and 209 marked unconverged): every check passed and no kernel bug came to light.  status <= 1 on every unpoisoned
 instance of all four launches; sens_status histograms [1974, 330, 0, 0] (ex and w) and [1496, 479, 0, 329] (ocp_vjp);
@@ -53,23 +53,21 @@ import numpy as np
 import pytest
 
 import sens_w_cases as C
+import sens_yardstick as Y
+from sens_yardstick import REC_N, REC_STATUS, REC_U, REC_W, REC_X
 
 torch = pytest.importorskip("torch")
-
-import test_gpu_vjp as TV  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 WANT = ("x", "u", "lam", "cost", "dx", "du", "gain")
-REC_STATUS, REC_N = TV.REC_STATUS, TV.REC_N
 _state = {}
 
 
 @pytest.fixture(scope="module")
 def Q():
     """The inputs of every test (never modified), the two engines and the poison masks."""
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
+    Y.require_gpu()
     from learningagileflight_se3_amd import scenario as S
     from learningagileflight_se3_amd.engine import Engine
     e50, e20 = Engine(), Engine(horizon=20)
@@ -208,14 +206,14 @@ def _record(Q):
 def test_solve_rec_does_not_depend_on_batch_position_or_size(Q):
     e, dev, B = Q["e50"], Q["e50"].device, Q["B"]
     big, idx, _ = _record(Q)
-    assert set(big) == {"x", "u", "lam", "cost", "status", "iters", "rec"} and big["rec"].shape == (B, TV.REC_W)
+    assert set(big) == {"x", "u", "lam", "cost", "status", "iters", "rec"} and big["rec"].shape == (B, REC_W)
     bad = torch.as_tensor(Q["nan7"], device=dev)
     assert bool((big["status"][bad] == 4).all()), torch.bincount(big["status"][bad]).tolist()
     assert bool((big["rec"][:, REC_STATUS] == big["status"].double()).all())
     assert bool((big["rec"][:, REC_N] == 50.0).all())
     good = ~bad
-    assert _same(big["rec"][good][:, TV.REC_X:TV.REC_X + 51 * 13].reshape(-1, 51, 13), big["x"][good])
-    assert _same(big["rec"][good][:, TV.REC_U:TV.REC_U + 50 * 4].reshape(-1, 50, 4), big["u"][good])
+    assert _same(big["rec"][good][:, REC_X:REC_X + 51 * 13].reshape(-1, 51, 13), big["x"][good])
+    assert _same(big["rec"][good][:, REC_U:REC_U + 50 * 4].reshape(-1, 50, 4), big["u"][good])
     _liveness("ocp_solve_rec", Q, big, Q["nan7"], idx, "rec")
     e.check_device()
 
@@ -261,8 +259,8 @@ def test_vjp_equals_the_contracted_jacobians_of_a_subset_launch(Q):
     it = torch.as_tensor(idx, device=e.device)
     grad = big["grad"].index_select(0, it).cpu().numpy()
     ss = big["sens_status"].index_select(0, it).cpu().numpy()
-    fwd = TV._np(e.ocp_sensitivity_w(sb["ini"][idx], sb["goal"][idx], sb["p"][idx], sb["a"][idx], t[idx],
-                                     weights=Q["Wp"][idx], want=("dx", "du")))
+    fwd = Y.to_numpy(e.ocp_sensitivity_w(sb["ini"][idx], sb["goal"][idx], sb["p"][idx], sb["a"][idx], t[idx],
+                                         weights=Q["Wp"][idx], want=("dx", "du")))
     e.check_device()
     assert fwd["dx"].shape == (len(idx), 33, 51, 13)
     # both routes factorise at the same point: the same verdict wherever the record was not edited
@@ -273,6 +271,6 @@ def test_vjp_equals_the_contracted_jacobians_of_a_subset_launch(Q):
           f"({int((~poisoned[idx]).sum())} unpoisoned)")
     assert live.sum() >= 0.9 * (~poisoned[idx]).sum()
     sel = {k: fwd[k][live] for k in ("dx", "du")}
-    ref, scale = TV._reference(sel, Q["g_x"][idx][live], Q["g_u"][idx][live])
-    worst = TV._relative(grad[live], ref, scale, f"ocp_vjp in a launch of {Q['B']} against ocp_sensitivity_w alone")
-    assert TV.ADJ_BAR <= 1e-5 and worst <= TV.ADJ_BAR
+    ref, scale = Y.vjp_reference(sel, Q["g_x"][idx][live], Q["g_u"][idx][live])
+    worst = Y.vjp_relative(grad[live], ref, scale, f"ocp_vjp in a launch of {Q['B']} against ocp_sensitivity_w alone")
+    assert Y.VJP_BAR <= 1e-5 and worst <= Y.VJP_BAR

@@ -3,7 +3,7 @@ to the ten weights, and the autograd layers' ``weights=`` (diff_mpc.mpc_layer, d
 
 Run on an MI355X:  python -m pytest tests/test_gpu_sens_w.py -m gpu -q -s
 
-Inputs, weight rows D and G and the finite-difference yardstick: tests/sens_w_cases.py.
+Inputs and weight rows D and G: tests/sens_w_cases.py; the finite-difference yardstick: tests/sens_yardstick.py.
 
 (a) Weight columns against central differences of the CPU oracle's solve at h_j = 1e-4 max(|w_j|, 1) and 2 h_j.  A
 (sample, weight) pair is admitted from the oracle alone (four solves with status <= 1, e = max|J_h - J_2h| / max|J_h|
@@ -55,46 +55,43 @@ import numpy as np
 import pytest
 
 import sens_w_cases as C
+import sens_yardstick as Y
 
 torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
 
-ADMIT = C.ADMIT
+ADMIT = Y.ADMIT
 # largest err - 10 e on the first GPU run, per case, and the bar: rounded up to the next power of ten (<= ADMIT)
 F_MEASURED = {"50D": 6.046e-04, "50G": 4.242e-04, "20G": 7.078e-05, "2G": 2.240e-09}
 F = {"50D": 1e-3, "50G": 1e-3, "20G": 1e-4, "2G": 1e-8}
 ADMITTED = {"50D": (148, 160), "50G": (73, 80), "20G": (72, 80), "2G": (24, 24)}
 ADJ_MEASURED = 1.225e-13   # largest |gain - du_0| / scale over the weight columns on the first GPU run
-ADJ_BAR = 1e-12          # ADJ_MEASURED rounded up to the next power of ten, at most 1e-5
-ADJ_BAR_ALL = 1e-6       # all 33 columns: tests/test_gpu_sens_ex.py's bar (first run here 3.190e-07)
+ADJ_BAR = Y.ADJ_BAR_WEIGHTS   # ADJ_MEASURED rounded up to the next power of ten, at most 1e-5
+ADJ_BAR_ALL = Y.ADJ_BAR       # all 33 columns: tests/test_gpu_sens_ex.py's bar (first run here 3.190e-07)
 ETA = 0.1                # the descent step, fixed on the oracle alone (module docstring)
+_np = Y.to_numpy
 NAMES = C.WEIGHT_NAMES
-WCOLS = slice(23, 33)
+WCOLS = Y.SL["weights"]
 ROWS4 = {"D": C.ROW_D, "G": C.ROW_G, "D+wqf": np.where(np.arange(10) == 5, 2.0, C.ROW_D),
          "G-wqf": np.where(np.arange(10) == 5, 0.0, C.ROW_G)}
 
 
 @pytest.fixture(scope="module")
 def eng():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
+    Y.require_gpu()
     from learningagileflight_se3_amd.engine import Engine
     return Engine()
 
 
 @pytest.fixture(scope="module")
 def sb():
-    return C.batch()
+    return Y.batch()
 
 
 def _args(sb, idx, t=None):
     t = sb["t"] if t is None else t
     return tuple(v[idx] for v in (sb["ini"], sb["goal"], sb["p"], sb["a"], t))
-
-
-def _np(out):
-    return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
 
 
 IDX24 = np.concatenate([np.arange(16), np.arange(8)])
@@ -112,28 +109,16 @@ def full24(eng, sb):
 @pytest.fixture(scope="module")
 def fd50(sb):
     """The oracle side of the N = 50 cases (about 13 s of CPU), computed once."""
-    t = C.case_t(sb, 50)
-    return {"50D": C.oracle_fd(sb, 16, 50, t, C.ROW_D), "50G": C.oracle_fd(sb, 8, 50, t, C.ROW_G)}
+    prob = {**sb, "t": C.case_t(sb, 50)}
+    return {"50D": Y.oracle_fd_weights(prob, 16, C.ROW_D, range(10), C.params_for(50)),
+            "50G": Y.oracle_fd_weights(prob, 8, C.ROW_G, range(10), C.params_for(50))}
 
 
-def _check_against_fd(J_gpu, sens_status, fd, case):
-    """err <= 10 e + F on the admitted pairs of instances with sens_status 0; prints every figure first."""
-    adm = fd["admitted"]
-    print(f"{case}: oracle admits {int(adm.sum())} of {adm.size} pairs; per column "
-          f"{dict(zip([NAMES[j] for j in fd['cols']], adm.sum(0).tolist()))}; sens_status histogram "
-          f"{np.bincount(sens_status, minlength=3).tolist()}")
-    use = adm & (sens_status == 0)[:, None]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        err = np.abs(J_gpu - fd["J"]).max(-1) / fd["scale"]
-    excess = np.where(use, err - 10 * fd["e"], -np.inf)
-    i, q = np.unravel_index(np.argmax(excess), excess.shape)
-    print(f"{case}: {int(use.sum())} pairs compared; max err {err[use].max():.3e}; max(err - 10 e) {excess.max():.3e} "
-          f"at sample {i} column {NAMES[fd['cols'][q]]} (err {err[i, q]:.3e}, e {fd['e'][i, q]:.3e}); "
-          f"median err {np.median(err[use]):.3e} (F {F[case]:.0e})")
-    assert (int(adm.sum()), adm.size) == ADMITTED[case]
-    assert (~adm).mean() <= 0.15, f"{case}: {int((~adm).sum())} of {adm.size} pairs not admitted"
-    assert use.sum() >= adm.sum() - adm.shape[1]          # at most one instance without a sensitivity
-    assert F[case] <= ADMIT and excess.max() <= F[case], (case, float(excess.max()), int(i), int(q))
+def _check_against_fd(J_gpu, sens_status, fd, case, cols=range(10)):
+    """sens_yardstick.check_against_fd under the case's F, and the oracle's admission count of the module docstring."""
+    assert F[case] <= ADMIT
+    Y.check_against_fd(J_gpu, sens_status, fd, case, F[case], names=[NAMES[j] for j in cols])
+    assert (int(fd["admitted"].sum()), fd["admitted"].size) == ADMITTED[case]
 
 
 # ---- (a) weight columns against the oracle's finite differences -----------------------------------------------
@@ -141,7 +126,7 @@ def _check_against_fd(J_gpu, sens_status, fd, case):
 def test_weight_columns_against_oracle_finite_differences_horizon_50(full24, fd50):
     assert np.all(full24["status"] <= 1) and np.all(full24["sens_status"] != 1)
     assert full24["columns"][23:] == list(NAMES) and full24["dx"].shape == (24, 33, 51, 13)
-    J = C.traj(full24["dx"][:, WCOLS], full24["du"][:, WCOLS])
+    J = Y.traj(full24["dx"][:, WCOLS], full24["du"][:, WCOLS])
     _check_against_fd(J[:16], full24["sens_status"][:16], fd50["50D"], "50D")
     _check_against_fd(J[16:], full24["sens_status"][16:], fd50["50G"], "50G")
 
@@ -152,13 +137,13 @@ def test_weight_columns_against_oracle_finite_differences_short(sb, horizon):
     n = 8 if horizon == 20 else 4
     cols = list(range(10)) if horizon == 20 else list(C.NON_TRAVERSAL)
     t = C.case_t(sb, horizon)
-    fd = C.oracle_fd(sb, n, horizon, t, C.ROW_G, cols)
+    fd = Y.oracle_fd_weights({**sb, "t": t}, n, C.ROW_G, cols, C.params_for(horizon))
     e = Engine(horizon=horizon)
     g = _np(e.ocp_sensitivity_w(*_args(sb, slice(0, n), t), weights=np.tile(C.ROW_G, (n, 1)), groups=("weights",),
                                 want=("x", "u", "dx", "du")))
     assert g["dx"].shape == (n, 10, horizon + 1, 13) and g["du"].shape == (n, 10, horizon, 4)
     assert np.all(g["dx"][:, :, 0, :] == 0.0) and np.all(np.isfinite(g["dx"])) and np.all(np.isfinite(g["du"]))
-    _check_against_fd(C.traj(g["dx"][:, cols], g["du"][:, cols]), g["sens_status"], fd, f"{horizon}G")
+    _check_against_fd(Y.traj(g["dx"][:, cols], g["du"][:, cols]), g["sens_status"], fd, f"{horizon}G", cols)
 
 
 # ---- (b) heterogeneous launch equals per-set launches ------------------------------------------------------------
@@ -211,28 +196,12 @@ def test_no_weights_and_the_contexts_own_row_equal_the_ex_launch(eng, sb):
 
 # ---- (c) adjoint against forward ------------------------------------------------------------------------------------
 
-def _adjoint_difference(g, label, cols=WCOLS, bar=ADJ_BAR):
-    """max over live instances of |gain[b, a, q] - du[b, q, 0, a]| / max|du[b, weight columns, 0, :]|."""
-    live = g["sens_status"] == 0
-    du0 = np.transpose(g["du"][:, :, 0, :], (0, 2, 1))[:, :, cols]             # (B, 4, 10)
-    gain = g["gain"][:, :, cols]
-    assert gain.shape == du0.shape and np.all(np.isfinite(gain)) and np.all(np.isfinite(du0))
-    diff = np.abs(gain - du0).max(axis=(1, 2))
-    scale = np.abs(du0).max(axis=(1, 2))
-    rel = np.where(scale > 0, diff / np.where(scale > 0, scale, 1.0), np.where(diff == 0, 0.0, np.inf))
-    rel = np.where(live, rel, 0.0)
-    b = int(np.argmax(rel))
-    per_col = np.abs(du0[live]).max(axis=(0, 1))
-    print(f"{label}: {int(live.sum())} of {live.size} instances live; max relative |gain - du_0| over the weight columns "
-          f"{rel.max():.3e} (sample {b}, scale {scale[b]:.3e}; bar {bar:.0e}); largest |du_0| per column "
-          f"{dict(zip(NAMES, (f'{v:.2e}' for v in per_col)))}")
-    assert live.sum() >= live.size - 1
-    return float(rel.max())
+W_ONLY, ALL33 = {"weights": WCOLS}, {"all": slice(0, 33)}      # the column groups of the identity's two bars
 
 
 def test_adjoint_gain_equals_forward_du0_horizon_50(eng, sb, full24):
     g = {k: (v[16:] if isinstance(v, np.ndarray) else v) for k, v in full24.items()}      # the row G instances
-    assert _adjoint_difference(g, "horizon 50") <= ADJ_BAR
+    assert Y.adjoint_difference(g, "horizon 50", W_ONLY, ADJ_BAR) <= ADJ_BAR
     only = _np(eng.ocp_sensitivity_w(*_args(sb, IDX24), weights=W24, want=("gain",)))
     assert set(only) == {"gain", "status", "iters", "sens_status", "columns"}
     assert np.array_equal(only["gain"], full24["gain"]) and np.array_equal(only["sens_status"], full24["sens_status"])
@@ -249,8 +218,8 @@ def test_adjoint_gain_equals_forward_du0_short(sb, horizon):
     g = _np(e.ocp_sensitivity_w(*_args(sb, slice(0, n), t), ul, weights=W, want=("u", "du", "gain")))
     assert g["du"].shape == (n, 33, horizon, 4) and g["gain"].shape == (n, 4, 33)
     assert np.all(np.isfinite(g["du"])) and np.all(np.isfinite(g["gain"]))
-    assert _adjoint_difference(g, f"horizon {horizon}") <= ADJ_BAR
-    assert _adjoint_difference(g, f"horizon {horizon}, all 33 columns", slice(0, 33), ADJ_BAR_ALL) <= ADJ_BAR_ALL
+    assert Y.adjoint_difference(g, f"horizon {horizon}", W_ONLY, ADJ_BAR) <= ADJ_BAR
+    assert Y.adjoint_difference(g, f"horizon {horizon}, all 33 columns", ALL33, ADJ_BAR_ALL) <= ADJ_BAR_ALL
     if horizon == 1:
         # one stage: the du_weight column is its u_last term alone, and it moves u_0
         live = g["sens_status"] == 0
@@ -265,14 +234,13 @@ def test_group_subsets_select_the_columns_of_the_full_launch(eng, sb, full24):
     from learningagileflight_se3_amd import _lib
     n = 4
     G = ("theta", "ini", "goal", "weights")
-    SL = {"theta": slice(0, 7), "ini": slice(7, 20), "goal": slice(20, 23), "weights": WCOLS}
     assert full24["columns"] == [c for g in G for c in _lib.SENS_COLUMNS_W[g]]
     assert np.all(full24["dx"][:, WCOLS, 0, :] == 0.0)                          # x_0 does not move with a weight
     ref = {k: full24[k][16:16 + n] for k in ("dx", "du", "gain")}                # row G, samples 0..3
     W = np.tile(C.ROW_G, (n, 1))
     for sel in (("weights",), ("weights", "theta"), ("weights", "ini"), ("goal", "weights"), G):
         out = _np(eng.ocp_sensitivity_w(*_args(sb, slice(0, n)), weights=W, groups=sel))
-        cols = np.concatenate([np.arange(33)[SL[g]] for g in G if g in sel])
+        cols = np.concatenate([np.arange(33)[Y.SL[g]] for g in G if g in sel])
         assert out["columns"] == [full24["columns"][c] for c in cols]
         assert out["dx"].shape == (n, len(cols), 51, 13) and out["gain"].shape == (n, 4, len(cols))
         assert np.array_equal(out["dx"], ref["dx"][:, cols]), sel

@@ -14,8 +14,8 @@ offsets the sweep used to compute from the lane index, at every horizon.
     on the odd instances (newton_cases.problem's convention); at least 99 % of the instances must solve, so that the
     comparison is one of full solves.
  2. Horizons.  The dumped Newton step solves the dense system of tests/newton.py at N = 1, 2, 3, 7 and 50 under the
-    bounds of test_gpu_chain_horizons.py (its helpers, its samples); N = 1 and 2 take the peeled stage 0 alone or after
-    one pass of the stage loop.
+    bounds of test_gpu_chain_horizons.py (newton_gpu.py's helpers, the same samples); N = 1 and 2 take the peeled stage
+    0 alone or after one pass of the stage loop.
  3. Both gradient kernels.  sol_gradient on 8 samples (synthetic_batch(8, seed=7)), FD and grad_mode = 1, twice on one
     context: out8, rewards9 and status9 of the second launch equal the first's bit for bit, and every solve converged.
 
@@ -28,11 +28,19 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import newton_cases as NC  # noqa: E402
-from test_gpu_chain_horizons import batch, horizon, step_solves_the_dense_system  # noqa: E402,F401
+from newton_gpu import horizon, step_solves_the_dense_system  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 OUT = ("x", "u", "lam", "cost", "status", "iters")
+
+
+@pytest.fixture(scope="module")
+def batch():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
+    from learningagileflight_se3_amd import scenario as S
+    return S.synthetic_batch(64, seed=2025)
 
 
 def _bits(a):
@@ -74,7 +82,7 @@ def test_workgroup_reuse(N):
 
 
 @pytest.mark.parametrize("N", (1, 2, 3, 7, 50))
-def test_horizons(batch, N):  # noqa: F811
+def test_horizons(batch, N):
     prob, ocases, gcases = horizon(batch, N)
     assert set(ocases) == set(gcases)
     step_solves_the_dense_system(f"N={N}", "-chain", prob, N, ocases, gcases)

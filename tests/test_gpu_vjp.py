@@ -37,29 +37,25 @@ import numpy as np
 import pytest
 
 import sens_w_cases as C
+import sens_yardstick as Y
+from sens_yardstick import REC_N, REC_STATUS, REC_U, REC_W, REC_X
 
 torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
 
 ADJ_MEASURED = 1.753e-07   # largest relative |grad - reference| of (1) on the first GPU run
-ADJ_BAR = 1e-6             # ADJ_MEASURED rounded up to the next power of ten, at most 1e-5
-GROUPS = ("theta", "ini", "goal", "weights")
-SL = {"theta": slice(0, 7), "ini": slice(7, 20), "goal": slice(20, 23), "weights": slice(23, 33)}
+ADJ_BAR = Y.VJP_BAR         # ADJ_MEASURED rounded up to the next power of ten, at most 1e-5
+GROUPS, SL = Y.GROUPS, Y.SL
 BIT = {"theta": 1, "ini": 2, "goal": 4, "weights": 8}
 NSAMPLES = {50: 16, 20: 8, 2: 8, 1: 8}
-REC_X, REC_U, REC_STATUS, REC_N, REC_W = 0, 663, 2221, 2222, 2223
-
-
-def _np(out):
-    return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+_np, _reference, _relative = Y.to_numpy, Y.vjp_reference, Y.vjp_relative
 
 
 @pytest.fixture(scope="module")
 def sb():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no CPU fallback by design)")
-    return C.batch()
+    Y.require_gpu()
+    return Y.batch()
 
 
 _CASES = {}
@@ -92,26 +88,6 @@ def _vjp(c, g_x, g_u, groups=GROUPS, rec=None):
     out = _np(c["eng"].ocp_vjp(*c["args"], c["rec"]["rec"] if rec is None else rec, g_x, g_u, groups=groups))
     torch.cuda.synchronize()
     return out
-
-
-def _reference(fwd, g_x, g_u):
-    """grad (B, 33) from the forward Jacobians, and the (B, 4) group scales max_q sum|dx||g_x| + sum|du||g_u|."""
-    ref = np.einsum("bqki,bki->bq", fwd["dx"], g_x) + np.einsum("bqka,bka->bq", fwd["du"], g_u)
-    mag = np.einsum("bqki,bki->bq", np.abs(fwd["dx"]), np.abs(g_x)) + \
-        np.einsum("bqka,bka->bq", np.abs(fwd["du"]), np.abs(g_u))
-    return ref, np.stack([mag[:, SL[g]].max(1) for g in GROUPS], 1)
-
-
-def _relative(grad, ref, scale, label):
-    """Largest |grad - ref| / group scale per group; a group with scale 0 must agree exactly.  Prints every figure."""
-    worst = {}
-    for j, g in enumerate(GROUPS):
-        diff = np.abs(grad[:, SL[g]] - ref[:, SL[g]]).max(1)
-        s = scale[:, j]
-        rel = np.where(s > 0, diff / np.where(s > 0, s, 1.0), np.where(diff == 0, 0.0, np.inf))
-        worst[g] = float(rel.max())
-    print(f"{label}: largest relative difference per group " + ", ".join(f"{g} {v:.3e}" for g, v in worst.items()))
-    return max(worst.values())
 
 
 def _all_live(c, out):

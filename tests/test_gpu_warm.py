@@ -507,7 +507,7 @@ def test_moving_gate_loop_warm(golden):
     from learningagileflight_se3_amd import moving_gate as MG
     from learningagileflight_se3_amd.engine import Engine
     from oracle import oracle as O
-    from test_moving_host import dnn2_from_fixture, fixture_episodes
+    from moving_cases import dnn2_from_fixture, fixture_episodes
     g = golden("moving")
     n_ep, steps = g["t"].shape
     assert (n_ep, steps) == (2, 120)

@@ -8,41 +8,9 @@ import torch
 from learningagileflight_se3_amd import moving_gate as MG
 from learningagileflight_se3_amd import scenario
 from learningagileflight_se3_amd.policy_net import Network
+from moving_cases import dnn2_from_fixture, episode_noise, per_sample
 
 V0, W0 = np.array([1.0, 0.3, 0.4]), np.pi / 2
-
-
-def dnn2_from_fixture(g):
-    net = Network(18, 128, 128, 7)
-    sd = {k: torch.as_tensor(g[k.replace(".", "_")]) for k in net.state_dict()}
-    net.load_state_dict(sd)
-    return net
-
-
-def per_sample(net):
-    """DNN2 evaluated one sample at a time in float32 on the CPU, as quad_nn.network.forward is called."""
-    def f(inp):
-        with torch.no_grad():
-            return np.stack([net(torch.tensor(r, dtype=torch.float)).numpy() for r in np.atleast_2d(inp)])
-    return f
-
-
-def episode_noise(s):
-    """np.random.seed(500 + s); nn_sample(); gate.move(...) draw order of make_golden.gen_moving."""
-    rs = np.random.RandomState(500 + s)
-    sample = scenario.nn_sample(rs)
-    return sample, MG.move_noise(rs, 500)
-
-
-def fixture_episodes(g):
-    """(samples, noise) of moving.npz's episodes: episode 0 runs last_inputs.npy's scenario (source 0), the
-    others nn_sample (source 1); the gate.move noise follows the same draw order for both."""
-    samples, noise = [], []
-    for s in range(g["inputs"].shape[0]):
-        smp, nz = episode_noise(s)
-        samples.append(g["inputs"][s] if g["source"][s] == 0 else smp)
-        noise.append(nz)
-    return np.stack(samples), np.stack(noise)
 
 
 def test_dnn2_fixture_is_the_trained_network(golden):

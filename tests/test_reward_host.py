@@ -5,7 +5,7 @@ the coverage of the GPU test's input generator, and d_min as a parameter.  No GP
 import numpy as np
 import pytest
 
-import test_gpu_reward as GR
+import reward_cases as GR
 from oracle import oracle as O
 
 

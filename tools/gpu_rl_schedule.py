@@ -102,7 +102,7 @@ for samples, dn32, o8, R9 in launches0:
     gate12 = scenario.gate_corners(samples[:, 7], samples[:, 8])
     oo8, oR9, _ = O.sol_gradient(ini, samples[:, 3:6], gate12, dn32)
     rr.append(np.abs(R9 - oR9) / np.maximum(np.abs(oR9), 1e-12))
-    # out8 on the north_star scale of the parity tests (tests/test_gpu_parity.py _grad_parity): |diff| / (1 + |ref|)
+    # out8 on the north_star scale of the parity tests (tests/parity_ref.py grad_parity): |diff| / (1 + |ref|)
     # -- the clipped FD entries are often exactly 0 or near it, where a raw relative error means nothing
     ro8.append(np.abs(o8[:, :7] - oo8[:, :7]) / (1.0 + np.abs(oo8[:, :7])))
 rr, ro8 = np.concatenate(rr), np.concatenate(ro8)
