@@ -83,7 +83,8 @@ constexpr int WS_CS = WS_Z + 14 * SX;            // [i][k] second-order-correcti
 constexpr int WS_SDX = WS_CS + NX * SX;          // original direction, kept while corrections are tried
 constexpr int WS_SDU = WS_SDX + NX * SX;
 constexpr int WS_SLP = WS_SDU + NU * SX;
-// compact factor record of stage k (backward_full [E], one 16-byte store per lane and stage):
+// compact factor record of stage k (riccati_mfma.inc backward_mfma, phase [E]: staged in S.kbuf, then one 16-byte
+// store per lane and stage):
 //   [RC_K, +68)  K_k^T [j][4]  feedback gain (K_k[a][j] at j * 4 + a)
 //   [RC_KF, +4)  k_k           feed-forward
 //   [RC_L, +10)  packed Cholesky factor of Quu_k (diagonal slots hold 1/l_jj)
@@ -98,18 +99,14 @@ constexpr int WS_RADJ = WS_PC + (MAXN + 1) * 18; // [k][16] right-hand side r_k 
 // [k][18] the costate identity's vector of stage k: p_k of a factorisation ([F]) or ph_k of a refinement sweep
 // (backward_chain), k = 1..N
 constexpr int WS_PVK = WS_RADJ + (MAXN + 1) * 16;
-// iterate / step trajectories (SoA [i][k], stride SX): only x and u stay in LDS (2 waves per SIMD need <= 20 KB)
+// step / multiplier trajectories (SoA [i][k], stride SX).  The step and the multipliers live in LDS (Smem::dx, du, lam,
+// lamp: WS_TRAJ); no kernel reads or writes these four ranges, which remain part of the slot stride (WS_SIZE)
 constexpr int WS_DX = WS_PVK + (MAXN + 1) * 18;  // Newton step dx [i][k]
-constexpr int WS_DU = WS_DX + NX * SX;           // du [a][k]  (must follow WS_DX: forward_chain stores x~ rows 0..16)
+constexpr int WS_DU = WS_DX + NX * SX;           // du [a][k]
 constexpr int WS_LAM = WS_DU + NU * SX;          // constraint multipliers lam [i][k]
 constexpr int WS_LAMP = WS_LAM + NX * SX;        // lam + dlam of the current step [i][k]
 constexpr int WS_FILT = WS_LAMP + NX * SX;       // filter (theta [0, FMAX), phi [FMAX, 2 FMAX))
-#ifdef LAFSE3_FAC_CHECK
-constexpr int WS_CHK = WS_FILT + 2 * FMAX;       // diagnostic build: copy of the VALU sweep's outputs (fac_check)
-constexpr int WS_END = WS_CHK + MAXN * (REC + PSTR) + (MAXN + 1) * 18;
-#else
 constexpr int WS_END = WS_FILT + 2 * FMAX;
-#endif
 // slot stride: whole 128-byte lines, an odd number of them (a stride with a large power-of-two factor puts one
 // offset of every slot in the same HBM channels: DESIGN.md §3.1b)
 constexpr int WS_SIZE0 = (WS_END + 15) & ~15;
@@ -206,32 +203,31 @@ struct Ctl {
     double ulo, uhi, wlo, whi;
 };
 
-// LDS of one instance (<= 20 KB: two workgroups per SIMD).  Only the iterate x / u (read by every
-// stage-parallel pass and every line-search trial) and the Riccati stage working set live here; the step,
-// the multipliers, the bound duals and the filter are in the HBM workspace (WS_*).
+// LDS of one instance (<= 40 KB: one workgroup per SIMD).  The iterate x / u, the step dx / du and the multipliers
+// lam / lamp (read by the stage-parallel passes and the line-search trials), the Riccati stage working set, the
+// per-instance constants and the factorisation sweep's per-lane tables live here; the bound duals, the filter and
+// everything per stage that the sweeps stream (table, records, P_k) are in the HBM workspace (WS_*).
 constexpr int RING = 24;                     // chain exchange slot (17 values, 16-byte aligned)
-constexpr int VGU = 44;                      // S.vec slot of g_u (16-byte aligned)
 struct __align__(16) Smem {
     double x[NX * SX], u[NU * SX];
     double dx[NX * SX], du[NU * SX];         // du must follow dx (forward_chain stores x~ rows 0..16 from dx)
     double lam[NX * SX], lamp[NX * SX];
-    alignas(16) double P[NA * PST];
-    double p[24];
+    alignas(16) double P[NA * PST];          // terminal value function P_N, p_N (terminal; the factorisation sweep takes
+    double p[24];                            // them into registers); the restoration sweep's value function (resto.inc)
     union {
-        struct {
-            double W[NA * GST];
+        struct {                             // one range, addressed from W: the factorisation sweep's LDS map
+            double W[NA * GST];              // (riccati_mfma.inc MF_*: table row, Qux columns, transpositions)
             double M[NZ * GST];
         };
         double ring[2 * RING];               // forward_chain: dx~_s, backward_chain: ph_s (two slots, s & 1)
         double tips[(MAXN + 1) * 12];        // reward: rotor tracks
         double rw[RW_SIZE];                  // restoration sweep: dense stage matrices (resto.inc)
     };
-    double gv[NZ * GLEN + 1];                // G column lists (riccati_tables.hpp)
-    double hv[64];                           // H~ upper nonzeros of the current stage
-    double hh[24];                           // h~ of the current stage
-    double cc[16];                           // c~ of the current stage
-    alignas(16) double vec[48];              // ph (0..16) | g: x~ entries (24..40), u entries (VGU..VGU+3)
-    alignas(16) double kbuf[REC];            // record staging: K_k^T [j][4] (68) | k_k (68..71)
+    double hv[64];                           // restoration sweep's small vectors (resto.inc: HV_*, hh[0] the pivot,
+    double hh[24];                           // cc = Quu, vec = c' | D | sqrt(D))
+    double cc[16];
+    alignas(16) double vec[48];
+    alignas(16) double kbuf[REC];            // record staging: K_k^T [j][4] (68) | k_k (68..71) | L_k (72..81)
     double wk[SX];
     // per-instance constants live in LDS so that the noinline phases read them with ds_read (a
     // reference to a private copy would be a flat load through scratch)
@@ -244,19 +240,13 @@ struct __align__(16) Smem {
     // per workgroup ahead of the instance loop (init_mf_tables) and read back by every sweep
     alignas(16) unsigned mfp[WAVE][4];       // packed-P store offsets of the lane's four P' entries
     unsigned short mfo[14][WAVE];            // Smem byte offsets: its gathers of G, H~ [4] and h~ [2], four LDS targets
-#ifdef LAFSE3_FAC_CHECK
-    double facd[4];                          // diagnostic: max relative difference MFMA vs VALU sweep (fac_check)
-#endif
 #ifdef LAFSE3_PHASE_TIMERS
     unsigned long long pt[24];               // debug phase timers and wait probes (s_memtime cycles)
     int timing;
 #endif
 };
 static_assert(sizeof(Smem) <= 160 * 1024 / 4, "Smem: one workgroup per SIMD (4 per CU) needs <= 40 KB of LDS");
-// per-lane write-only slot of the branch-free Riccati stores (lanes past the end of a work list): M's lower
-// triangle rows 17..20, columns 0..16, which no phase reads or writes
-__device__ inline double *dummy_slot(Smem &S) { return &S.M[(NA + lane_id() / NA) * GST + lane_id() % NA]; }
-// 16-byte LDS pieces (ds_read/write_b128) of the Riccati stage: P rows, M's u block, K^T rows, staging
+// 16-byte LDS pieces (ds_read/write_b128) of the Riccati stage: the sweep's LDS map from W, K^T rows, staging
 static_assert(offsetof(Smem, P) % 16 == 0 && offsetof(Smem, W) % 16 == 0 && offsetof(Smem, M) % 16 == 0 &&
               offsetof(Smem, kbuf) % 16 == 0, "Smem: 16-byte aligned Riccati arrays");
 
@@ -410,19 +400,6 @@ __device__ inline int opaque_lane()
     int l = lane_id();
     asm volatile("" : "+v"(l));
     return l;
-}
-
-// 1/sqrt(d) for d > 0: hardware estimate refined by two Newton steps (quadratic convergence from ~2^-22 to
-// full double precision; agrees with a correctly rounded 1/sqrt(d) to about an ulp).  d <= 0 is a failed
-// inertia test upstream; it is clamped only to keep the arithmetic finite.
-__device__ inline double rsqrt_nr(double d)
-{
-    d = fmax(d, 1e-300);
-    double y = __builtin_amdgcn_rsq(d);
-    const double hd = 0.5 * d;
-    y = y * fma(-hd * y, y, 1.5);
-    y = y * fma(-hd * y, y, 1.5);
-    return y;
 }
 
 // x = Quu^{-1} b with the packed Cholesky factor L (l00 l10 l11 l20 l21 l22 l30 l31 l32 l33) and the
@@ -743,60 +720,10 @@ __device__ __attribute__((always_inline)) inline double kkt_residual(const Model
     return nres / (fmin(nsol, 1e6 * nrhs) + nrhs);
 }
 
-// attribution builds (tools/gpu_attrib.sh): a phase repeated R times per call (every phase is idempotent),
-// the bench difference to the plain build is the phase's cost
-// the factorisation sweep on the f64 matrix cores (riccati_mfma.inc); 0: the VALU stage of riccati.inc
-#ifndef LAFSE3_MFMA
-#define LAFSE3_MFMA 1
-#endif
-#ifdef LAFSE3_FAC_CHECK
-// diagnostic build (tools/fac_check.py): both factorisation sweeps on the same Newton system; the MFMA sweep's
-// record / P_k / p_k are compared with the VALU sweep's (max |difference| / max |VALU value| per array, the worst
-// over the solve in S.facd; [3] counts inertia-test disagreements), then the VALU sweep's outputs are restored so
-// that the solve follows the VALU build's iterates exactly
-__device__ __noinline__ int fac_check(const Model &M, const Attitude &at, Smem &S, const Ctl &C, gdouble *ws, double dw,
-                                      int lsq)
-{
-    const int lane = lane_id();
-    const int N = C.N;
-    const int ok_old = backward_full(M, at, S, C, ws, dw, lsq);
-    gdouble *chk = ws + WS_CHK;
-    const int nr = N * REC, np = N * PSTR, nv = (N + 1) * 18;
-    for (int e = lane; e < nr; e += WAVE) chk[e] = ws[WS_REC + e];
-    for (int e = lane; e < np; e += WAVE) chk[nr + e] = ws[WS_PST + e];
-    for (int e = lane; e < nv; e += WAVE) chk[nr + np + e] = ws[WS_PVK + e];
-    vm_sync();
-    const int ok_new = backward_mfma(M, at, S, C, ws, dw, lsq);
-    vm_sync();
-    if (ok_old && ok_new) {
-        const int base[3] = {WS_REC, WS_PST, WS_PVK}, off[3] = {0, nr, nr + np}, n[3] = {nr, np, nv};
-        for (int a = 0; a < 3; ++a) {
-            double d = 0.0, m = 0.0;
-            for (int e = lane; e < n[a]; e += WAVE) {
-                const double o = chk[off[a] + e], v = ws[base[a] + e];
-                d = fmax(d, fabs(v - o));
-                m = fmax(m, fabs(o));
-                if (v != v) d = 1e300;
-            }
-            d = wmax(d);
-            m = wmax(m);
-            if (lane == 0) S.facd[a] = fmax(S.facd[a], d / fmax(m, 1e-300));
-        }
-    } else if (ok_old != ok_new) {
-        if (lane == 0) S.facd[3] += 1.0;
-    }
-    for (int e = lane; e < nr; e += WAVE) ws[WS_REC + e] = chk[e];
-    for (int e = lane; e < np; e += WAVE) ws[WS_PST + e] = chk[nr + e];
-    for (int e = lane; e < nv; e += WAVE) ws[WS_PVK + e] = chk[nr + np + e];
-    vm_sync();
-    return ok_old;
-}
-#endif
-
 // ---- linear solves of the Newton system --------------------------------------------------------------
 // One non-inlined function holds every sweep of a Newton-system solve, each inlined exactly once in one loop (the
 // costates pass twice: the solve's and the refinement step's):
-//   factor:  build_table + backward_full (factorisation) then forward_chain; otherwise the right-hand side
+//   factor:  build_table + backward_mfma (factorisation) then forward_chain; otherwise the right-hand side
 //            (rq, rr, rc) already in the workspace goes through backward_chain + forward_chain.  factor = 2:
 //            an inertia-correction retry (other delta_w, same iterate): the stage table, which does not hold
 //            delta_w, is reused (72 % of IPM iterations retry at least once)
@@ -875,23 +802,17 @@ __device__ __noinline__ int linear_solve(const Model &M, const Attitude &at, Sme
         if (fac) {
             if (factor != 2) build_table(M, at, S, C, ws, lsq);   // 2: inertia retry, the table is current
             PT_END(S, 2);
-            int okf = 1;
-#ifdef LAFSE3_FAC_CHECK
-            okf = fac_check(M, at, S, C, ws, dw, lsq);
-#else
-            for (int r = 0; r < 1; ++r) okf = LAFSE3_MFMA ? backward_mfma(M, at, S, C, ws, dw, lsq)
-                                                                       : backward_full(M, at, S, C, ws, dw, lsq);
-#endif
+            const int okf = backward_mfma(M, at, S, C, ws, dw, lsq);
             if (!okf) {
                 sweeps++;
                 return 0;
             }
             PT_END(S, 3);
         } else {
-            for (int r = 0; r < 1; ++r) backward_chain(M, S, C, ws);
+            backward_chain(M, S, C, ws);
             PT_END(S, 7);
         }
-        for (int r = 0; r < 1; ++r) forward_chain(M, S, C, ws, fac);
+        forward_chain(M, S, C, ws, fac);
         PT_END(S, 4);
         // a refinement sweep (step >= 0; never a factorisation) adds the solution it started from
         if (step >= 0) costates_identity<true>(S, C, ws, 0, bk);
@@ -901,8 +822,7 @@ __device__ __noinline__ int linear_solve(const Model &M, const Attitude &at, Sme
         if (step < 0 && dump_pre) dump_step(S, ws, C.N, dump_pre);
         PT_END(S, 11);
         if (!refine) break;
-        double nr = 0.0;
-        for (int r = 0; r < 1; ++r) nr = kkt_residual(M, at, S, C, ws, dw, soc);
+        const double nr = kkt_residual(M, at, S, C, ws, dw, soc);
         PT_END(S, 6);
         if (step < 0) {
             ratio = nr;
@@ -1882,7 +1802,6 @@ __device__ __noinline__ int ift_probes(const lafse3_params &prm, const Model &M,
 #include "warm.inc"
 
 // ------------------------------------------------------------------------------------------------
-// waves per SIMD the register allocation targets (LDS admits 2: Smem <= 20 KB)
 // One NLP instance (or one scored trajectory) on this wave, with the workspace slot ws.
 // Returns the instance's IPM iteration count (0 for trajectory scoring).
 // DUMP (ipm_kernel_dump): the debug dump also records the iterate (dump_point); ipm_kernel compiles none of that.
@@ -2016,9 +1935,6 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
     S.timing = (A.ptime != nullptr);
     if (lane < 24) S.pt[lane] = 0ull;
 #endif
-#ifdef LAFSE3_FAC_CHECK
-    if (lane < 4) S.facd[lane] = 0.0;
-#endif
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
     PT_BEGIN(S);
     if (lane < 3) {
@@ -2092,7 +2008,6 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
         if (warm)
             warm_load_primal(S, wrec, A.ini + b * NX, ZW->shift, ZW->bound_push, ZW->bound_frac, prm.dt, tt, w_peak,
                              w_decay);
-    init_gv_const(M, S);
     vm_sync();
     // ---- gradient-based objective scaling
     {
@@ -2616,9 +2531,6 @@ __device__ __attribute__((always_inline)) inline int run_instance(const KernelAr
 #ifdef LAFSE3_PHASE_TIMERS
     if (A.ptime && lane < 16) A.ptime[inst * PT_COLS + lane] = S.pt[lane];
     if (A.ptime && lane >= 16 && lane < 24) A.ptime[inst * PT_COLS + 8 + lane] = S.pt[lane];
-#endif
-#ifdef LAFSE3_FAC_CHECK
-    if (A.ptime && lane < 4) A.ptime[inst * PT_COLS + lane] = (unsigned long long)__double_as_longlong(S.facd[lane]);
 #endif
     if (A.ptime && lane == 0) {
         // placement record: start / end (100 MHz s_memrealtime), HW_ID (wave/simd/cu/se), XCC_ID

@@ -4,18 +4,18 @@
 // state augmented by the previous control (the ||U_k - U_{k-1}||^2 term couples stages):
 //   min sum_k 1/2 z_k^T H~_k z_k + h~_k^T z_k   s.t. dx~_{k+1} = G_k z_k + c~_k,  z_k = [dx~_k; du_k]
 //
+// The factorisation sweep itself (W = P G, M = G^T W + H~, Cholesky of Quu, K, k, P, p per stage) is
+// riccati_mfma.inc backward_mfma; this file holds what stands around it:
+// buffer helpers    wave-uniform workspace bases and the buffer loads / stores the sweeps step through HBM with
 // build_table       stage-parallel (lane = stage): G_k's 54 stage-dependent entries, H~_k's 62 upper
 //                   nonzeros (cost Hessian + lambda-Hessian of f_d + barrier Sigma), h~_k, c~_k  -> HBM table
-// backward_full     sequential over k, 64 lanes per stage on the VALU: W = P G (column lists, 7 terms),
-//                   M = G^T W + H~ (upper triangle), Cholesky of Quu (inertia test), K, k, P, p; per stage the
-//                   factor record (K_k^T, k_k, L_k), P_k packed and p_k.  The MFMA form of the same stage is
-//                   riccati_mfma.inc backward_mfma (the default, LAFSE3_MFMA).
-// backward_chain    iterative-refinement right-hand side with the last factorisation: P_s c~_{s-1}
-//                   stage-parallel, then ph_s = A~^T ph_{s+1} + rq_s + K_s^T g_s + P_s c~_{s-1} per stage
+// terminal          the value function at stage N (P_N, p_N -> S.P / S.p, packed P_N -> HBM), where the
+//                   factorisation sweep and a refinement sweep start
+// gslot, gconst, make_atab   A~ by rows and by columns: every coefficient's table slot or constant, for the chains
 // forward_chain     du_s = K_s x~_s + k_s, dx_{s+1} = A~ dx_s + B~ du_s + c_s per stage
 // costates_identity lam+_{k-1} = (P_k dx~_k + p_k)[x rows] stage-parallel (no adjoint recursion)
-
-__constant__ HTab c_htab = make_htab();
+// backward_chain    iterative-refinement right-hand side with the last factorisation: P_s c~_{s-1}
+//                   stage-parallel, then ph_s = A~^T ph_{s+1} + rq_s + K_s^T g_s + P_s c~_{s-1} per stage
 
 __device__ inline dvec2 dv2(double a, double b)
 {
@@ -264,78 +264,6 @@ __device__ __attribute__((always_inline)) inline void build_table(const Model &M
     vm_sync();
 }
 
-// per-instance constant part of the G column lists (identity entries, dt, rotor torque map)
-__device__ void init_gv_const(const Model &M, Smem &S)
-{
-    const int lane = opaque_lane();
-    for (int e = lane; e < NZ * GLEN; e += WAVE) {
-        const int j = e / GLEN, t = e % GLEN;
-        double v = 0.0;
-        if (j < 3) v = (t == 0) ? 1.0 : 0.0;
-        else if (j < 6) v = (t == 0) ? M.dt : (t == 1 ? 1.0 : 0.0);
-        else if (j < 10) v = (t == 3 + (j - 6)) ? 1.0 : 0.0;
-        else if (j < 13) v = (t == 4 + (j - 10)) ? 1.0 : 0.0;
-        else if (j >= 17) {
-            const int a = j - 17;
-            if (t >= 3 && t < 6) v = Bw(M, t - 3, a);
-            else if (t == 6) v = 1.0;
-        }
-        S.gv[e] = v;
-    }
-}
-
-// The same scatter with its three LDS targets per lane computed once per sweep (scatter_offsets, byte offsets
-// in Smem; lanes without a t2 value write their dummy slot, the unused lower triangle of M's u rows): three
-// unconditional stores per stage instead of the per-stage index arithmetic and exec-mask branches above.
-struct ScatterOff {
-    int o0, o1, o2;
-};
-__device__ inline ScatterOff scatter_offsets(Smem &S)
-{
-    const int lane = opaque_lane();
-    char *b = (char *)&S;
-    double *p0 = (lane < NGV) ? &S.gv[gv_col(lane) * GLEN + gv_pos(lane)] : &S.hv[lane - NGV];
-    double *p1 = (lane < 52) ? &S.hv[10 + lane] : &S.hh[lane - 52];
-    double *p2 = (lane < 9) ? &S.hh[12 + lane] : ((lane < 22) ? &S.cc[lane - 9] : dummy_slot(S));
-    return ScatterOff{(int)((char *)p0 - b), (int)((char *)p1 - b), (int)((char *)p2 - b)};
-}
-__device__ inline void scatter_stage_at(Smem &S, const ScatterOff &o, const double t0, const double t1,
-                                        const double t2)
-{
-    char *b = (char *)&S;
-    *(double *)(b + o.o0) = t0;
-    *(double *)(b + o.o1) = t1;
-    *(double *)(b + o.o2) = t2;
-}
-
-// M = G^T W + H~ is stored with its u block (G/M columns 17..20) one column to the right, at MU = 18, so that
-// the Qux / Quu rows start 16-byte aligned (GST even): M(i, j) at S.M[i * GST + mcol(j)]
-constexpr int MU = NA + 1;
-__device__ constexpr int mcol(int j) { return j >= NA ? j + 1 : j; }
-static_assert(GST % 2 == 0 && MU % 2 == 0 && MU + NU <= GST, "aligned u block of M");
-
-__device__ inline void load_row(const gdouble *tab, int k, double &t0, double &t1, double &t2)
-{
-    const int lane = opaque_lane();
-    const gdouble *row = tab + (size_t)k * TB_W;
-    // unconditional (clamped) loads: a branch around a load makes the vmcnt bookkeeping path-dependent
-    // and the compiler then drains every outstanding load AND store with vmcnt(0) before the first use
-    t0 = row[lane];
-    t1 = row[64 + lane];
-    t2 = row[128 + min(lane, 23)];
-}
-
-// factor record k (K_k^T, k_k: RC_L doubles staged in S.kbuf by [E]) -> HBM, one 16-byte store per lane; [E]
-// stores L_k itself
-__device__ inline void flush_rec(const Smem &S, gdouble *Rec, int k)
-{
-    constexpr int NP = RC_L / 2;
-    static_assert(NP <= WAVE, "record: one store per lane");
-    const int lane = opaque_lane();
-    const dvec2 v = ((const dvec2 *)S.kbuf)[min(lane, NP - 1)];
-    if (lane < NP) ((gdvec2 *)(Rec + (size_t)k * REC))[lane] = v;
-}
-
 // ---- terminal value function ------------------------------------------------------------------------
 __device__ inline double sel3(const double *v, int c) { return c == 0 ? v[0] : (c == 1 ? v[1] : v[2]); }
 __device__ void terminal(const Model &M, const Attitude &at, Smem &S, const Ctl &C, gdouble *ws, double dw,
@@ -414,309 +342,6 @@ __device__ void terminal(const Model &M, const Attitude &at, Smem &S, const Ctl 
             if (e3 < NUP17) ws[WS_PST + pst_at(N - 1, e3)] = S.P[c_up.i17[e3] * PST + c_up.j17[e3]];
         }
     }
-}
-
-// ---- backward sweep (factorisation) -----------------------------------------------------------------
-// Returns 1 on success, 0 when some Quu is not positive definite (wrong inertia).
-__device__ __attribute__((always_inline)) inline int backward_full(const Model &M, const Attitude &at, Smem &S, const Ctl &C, gdouble *ws,
-                                          double dw, int mode_lsq)
-{
-    const int lane = opaque_lane();
-    const int N = C.N;
-    const gdouble *tab = ws + WS_TAB;
-    gdouble *Pst = ws + WS_PST;
-    gdouble *Rec = ws + WS_REC;
-    if (lane == 0) S.gv[NZ * GLEN] = 0.0;   // zero slot for the absent entries of an A~ column
-    terminal(M, at, S, C, ws, dw, mode_lsq, 0);
-    int pi_[3], pj_[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const int e3 = lane + 64 * r;
-        pi_[r] = (e3 < NUP17) ? c_up.i17[e3] : 0;
-        pj_[r] = (e3 < NUP17) ? c_up.j17[e3] : 0;
-    }
-    // [C]/[D] lane roles: lane L < 51 takes active column cA = L % 17 (x 0..12, u 13..16 -> G column wj) and
-    // row group grp = L / 17; lanes 51..63 repeat lanes 0..12 (identical values to identical addresses).
-    // [C]: W rows 6 grp .. 6 grp + 5 of G column wj, stored in W's column cA (active index).  [D]: the 153
-    // upper entries of M are split by a regular tournament on the 17 active columns (circulant: column cA
-    // forms M(cA, cA + d mod 17) for d = 0..8, lane group grp the three d = 3 grp .. 3 grp + 2), so that each
-    // lane sums with the G column list it already holds from [C] (no G reads in [D]):
-    //   M(cA, oA) = sum_t G_t(wj) W[row_t(wj)][oA] + H~,  stored at the upper position of (wj, G column of oA).
-    const int Lr = lane < 3 * NA ? lane : lane - 3 * NA;
-    const int cA = Lr % NA, grp = Lr / NA;
-    const int wj = cA < NX ? cA : cA + NU;
-    const int gi = (lane >= NA && lane < NA + NU) ? NX + (lane - NA) : wj;   // g entry: lanes 17..20 take u_prev
-    // Branch-free index tables, hoisted out of the stage loop: a G column list's padding slots carry a
-    // zero coefficient, so their row index is clamped to 0 and the product contributes exactly 0 (the
-    // per-term `if (row >= 0)` made every LDS read divergent and unbatchable).
-    int wcol[GLEN];
-#pragma unroll
-    for (int t = 0; t < GLEN; ++t) wcol[t] = max(g_row(wj, t), 0);
-    // [D] computes only the 153 upper entries of M among the active columns x (0..12) and u (17..20): the
-    // u_prev rows/columns 13..16 of G are empty, so there M = H~ (the +-2 du_w s coupling, the same on every
-    // stage) and those entries are written once below.  Per lane 3 entries: W column, M offset, H~ slot and
-    // delta_w flags (one word).
-    unsigned mhf[3];
-    int moff[3], mwc[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const int oA = (cA + 3 * grp + r) % NA;
-        const int wo = oA < NX ? oA : oA + NU;
-        const int i = min(wj, wo), j = max(wj, wo);
-        moff[r] = i * GST + mcol(j);
-        mwc[r] = oA;
-        const int mh = c_htab.idx[i * 21 + j];
-        const int fl = (mh >= 0) ? (int)c_htab.e[mh].flag : 0;
-        mhf[r] = (unsigned)((mh >= 0) ? mh : NHV) | ((unsigned)fl << 8);   // S.hv[NHV] is a zero slot
-    }
-    if (lane == 0) { S.hv[NHV] = 0.0; S.hv[NHV + 1] = 0.0; }
-    // per-lane constants of the stage loop, formed once per sweep: delta_w terms of the three M entries
-    // (dw or 0 on H~'s diagonal: h = hv + fma(dwk, kx, dwc) adds exactly what the flags select), the LDS targets
-    // of [C]'s six W stores and [D]'s g store (g's u entries at the 16-byte aligned S.vec[VGU]), and [E]'s
-    // right-hand-side row (Qux column j = M row j's u block, or g_u)
-    double dwc[3], dwk[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const unsigned fl = (mhf[r] >> 8) & 3u;
-        dwc[r] = (fl == 2u) ? dw : 0.0;
-        dwk[r] = (fl == 1u) ? dw : 0.0;
-    }
-    int wdst[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        const int i = 6 * grp + c;
-        wdst[c] = (int)(((i < NA) ? (char *)&S.W[i * GST + cA] : (char *)dummy_slot(S)) - (char *)&S);
-    }
-    const int gdst = (int)((char *)((gi < NA) ? &S.vec[24 + gi] : &S.vec[VGU + gi - NA]) - (char *)&S);
-    const int rhs_off = (int)((lane < NA ? (char *)&S.M[lane * GST + MU] : (char *)&S.vec[VGU]) - (char *)&S);
-    // [D]'s 21 W read addresses (the compiler otherwise re-forms them with 21 adds every stage); opaque so that
-    // they stay in registers
-    int waddr[3][GLEN];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int t = 0; t < GLEN; ++t) {
-            waddr[r][t] = (int)((char *)&S.W[wcol[t] * GST + mwc[r]] - (char *)&S);
-            asm volatile("" : "+v"(waddr[r][t]));
-        }
-
-    const ScatterOff so = scatter_offsets(S);
-#define SCATTER_STAGE() scatter_stage_at(S, so, t0, t1, t2)
-    double t0, t1, t2;
-    load_row(tab, N - 1, t0, t1, t2);
-    SCATTER_STAGE();
-    load_row(tab, max(N - 2, 0), t0, t1, t2);   // stage N-2's row, scattered in [E] of stage N-1
-    sync();
-    // constant M entries of the u_prev rows and columns (13..16, upper triangle): H~'s u~-u~ diagonal
-    // (slots 50..53) and u~-u coupling (slots 54..57), zero elsewhere (G has no u_prev column; no delta_w on
-    // u_prev: riccati_tables.hpp flags)
-    for (int e = lane; e < NZ * NZ; e += WAVE) {
-        const int i = e / NZ, j = e % NZ;
-        const bool up = (i >= NX && i < NA) || (j >= NX && j < NA);
-        if (j >= i && up) {
-            double v = 0.0;
-            if (i >= NX && j == i) v = S.hv[50 + i - NX];
-            if (i >= NX && i < NA && j == i + NU) v = S.hv[54 + i - NX];
-            S.M[i * GST + mcol(j)] = v;
-        }
-    }
-    PT_BEGIN(S);
-    for (int k = N - 1; k >= 0; --k) {
-        // [A] (the table row of stage k-1 is already in t0..t2: loaded in [E] of the previous iteration, ahead
-        // of that iteration's stores, so that its scatter in [E] below waits for the loads only — gfx9 counts
-        // loads and stores on one in-order vmcnt)
-        PT_END(S, 12);
-        // [C] ph = p + P c~ ; W = P G
-        // Branch-free throughout the stage: lanes past the end of a work list recompute its last item and
-        // store the identical value to the identical LDS address (a branch per store would split the stage
-        // into basic blocks the scheduler cannot interleave across, plus exec-mask SALU work)
-        // software-pipelined W = P G: the G list and the first two P row pieces are requested before the ph
-        // chain, and each row's pieces two rows ahead of their use (sched_barrier fences keep
-        // the order: under the register budget the scheduler otherwise waits on every row's reads in turn)
-        double gval[GLEN];
-        {
-            constexpr int D = 2;
-            dvec2 qb[D][3];
-#pragma unroll
-            for (int t = 0; t < GLEN; ++t) gval[t] = S.gv[wj * GLEN + t];
-#pragma unroll
-            for (int t = 0; t < D; ++t) {
-                const dvec2 *pr = (const dvec2 *)&S.P[wcol[t] * PST + 6 * grp];
-                qb[t][0] = pr[0]; qb[t][1] = pr[1]; qb[t][2] = pr[2];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                const int li = min(lane, NA - 1);
-                double acc = S.p[li];
-#pragma unroll
-                for (int m = 0; m < NX; ++m) acc += S.P[li * PST + m] * S.cc[m];
-                S.vec[li] = acc;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            double acc[6];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) acc[c] = 0.0;
-#pragma unroll
-            for (int t = 0; t < GLEN; ++t) {
-                const dvec2 q0 = qb[t % D][0], q1 = qb[t % D][1], q2 = qb[t % D][2];
-                acc[0] = fma(q0.x, gval[t], acc[0]);
-                acc[1] = fma(q0.y, gval[t], acc[1]);
-                acc[2] = fma(q1.x, gval[t], acc[2]);
-                acc[3] = fma(q1.y, gval[t], acc[3]);
-                acc[4] = fma(q2.x, gval[t], acc[4]);
-                acc[5] = fma(q2.y, gval[t], acc[5]);
-                if (t + D < GLEN) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    const dvec2 *pr = (const dvec2 *)&S.P[wcol[t + D] * PST + 6 * grp];
-                    qb[t % D][0] = pr[0]; qb[t % D][1] = pr[1]; qb[t % D][2] = pr[2];
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 6; ++c) *(double *)((char *)&S + wdst[c]) = acc[c];
-        }
-        sync();
-        // [D] g = G^T ph + h~ ; M = G^T W + H~ (upper triangle)
-        {
-            // every LDS read of [D] requested at once (g's ph entries, the three W column pieces, the H~ slots),
-            // then the four sums: one wait instead of one per sum
-            const double kx = (k >= 1) ? 1.0 : 0.0;
-            double vv[GLEN], wv[3][GLEN], hv[3];
-            const double hw = S.hh[wj], hu = S.hh[gi];
-#pragma unroll
-            for (int t = 0; t < GLEN; ++t) vv[t] = S.vec[wcol[t]];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-#pragma unroll
-                for (int t = 0; t < GLEN; ++t) wv[r][t] = *(const double *)((const char *)&S + waddr[r][t]);
-                hv[r] = S.hv[mhf[r] & 255u];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            double acc = hw;
-#pragma unroll
-            for (int t = 0; t < GLEN; ++t) acc += gval[t] * vv[t];
-            *(double *)((char *)&S + gdst) = (gi == wj) ? acc : hu;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                double a = 0.0;
-#pragma unroll
-                for (int t = 0; t < GLEN; ++t) a += gval[t] * wv[r][t];
-                double h = hv[r] + fma(dwk[r], kx, dwc[r]);
-                a += h;
-                S.M[moff[r]] = a;
-            }
-        }
-        sync();
-        PT_END(S, 13);
-        // the next stage's tile goes in right away so that [E]'s chain is not behind it
-        PT_WAIT(S, 0, 0);   // timer build: the wait for the tile's loads (the compiler's count here is 0)
-        SCATTER_STAGE();   // next stage's tile ([E], [F] read only M, vec, kbuf)
-        load_row(tab, max(k - 2, 0), t0, t1, t2);   // the tile after that, issued before [F]'s stores
-        // [E] Cholesky of Quu (every lane), gains.  The right-hand sides are read with Quu so that their LDS
-        // latency hides under the Cholesky chain; the inertia test (ok) is taken at the end of [E] (a failed
-        // factorisation only writes gains that the retry overwrites), keeping [E] one basic block.
-        int ok = 1;
-        // Qux column j (M row j, u block 16-byte aligned at MU) or g_u (S.vec[VGU])
-        const dvec2 *mrow = (const dvec2 *)((const char *)&S + rhs_off);
-        const dvec2 m01 = mrow[0], m23 = mrow[1];
-        double b0 = m01.x, b1 = m01.y, b2 = m23.x, b3 = m23.y;
-        double L[10], iL[4];
-        {
-            const double q00 = S.M[17 * GST + MU], q01 = S.M[17 * GST + MU + 1], q02 = S.M[17 * GST + MU + 2], q03 = S.M[17 * GST + MU + 3];
-            const double q11 = S.M[18 * GST + MU + 1], q12 = S.M[18 * GST + MU + 2], q13 = S.M[18 * GST + MU + 3];
-            const double q22 = S.M[19 * GST + MU + 2], q23 = S.M[19 * GST + MU + 3], q33 = S.M[20 * GST + MU + 3];
-            // every Quu / right-hand-side read issued before the pivot chain (the scheduler otherwise issued the
-            // rows 18..20 reads after the first pivot and waited on them before the third: 550 -> 546 ms)
-            __builtin_amdgcn_sched_barrier(0);
-            // L packed: l00 l10 l11 l20 l21 l22 l30 l31 l32 l33; only the reciprocal diagonal 1/l_jj is
-            // needed (off-diagonals and solves multiply by it), computed as a Newton-refined reciprocal
-            // square root (~9 dependent ops instead of a correctly rounded sqrt plus a division, ~27); the
-            // oracle's 1/sqrt(d) agrees to rounding.  The diagonal slots of L hold 1/l_jj.
-            double d = q00;
-            if (!(d > 0.0)) ok = 0;
-            iL[0] = rsqrt_nr(d);
-            L[1] = q01 * iL[0];
-            L[3] = q02 * iL[0];
-            L[6] = q03 * iL[0];
-            d = q11 - L[1] * L[1];
-            if (!(d > 0.0)) ok = 0;
-            iL[1] = rsqrt_nr(d);
-            L[4] = (q12 - L[3] * L[1]) * iL[1];
-            L[7] = (q13 - L[6] * L[1]) * iL[1];
-            d = q22 - L[3] * L[3] - L[4] * L[4];
-            if (!(d > 0.0)) ok = 0;
-            iL[2] = rsqrt_nr(d);
-            L[8] = (q23 - L[6] * L[3] - L[7] * L[4]) * iL[2];
-            d = q33 - L[6] * L[6] - L[7] * L[7] - L[8] * L[8];
-            if (!(d > 0.0)) ok = 0;
-            iL[3] = rsqrt_nr(d);
-            L[0] = iL[0]; L[2] = iL[1]; L[5] = iL[2]; L[9] = iL[3];
-        }
-        {
-            // straight-line: lane j < 17 solves column j of Qux, lanes >= 17 all solve g_u (identical values, so
-            // their duplicate stores are benign); per-lane base/stride addressing instead of branches
-            chol4_solve(L, iL, b0, b1, b2, b3);
-            // K^T rows [j][4] (j < 17) and k_k at [17][4]: 16-byte pieces, lanes >= 17 duplicate k_k
-            dvec2 *kb = (dvec2 *)&S.kbuf[min(lane, NA) * NU];
-            kb[0] = dv2(-b0, -b1);
-            kb[1] = dv2(-b2, -b3);
-            // L_k straight to its record (every lane holds it: identical values to identical addresses)
-            gdvec2 *lr = (gdvec2 *)(Rec + (size_t)k * REC + RC_L);
-#pragma unroll
-            for (int e = 0; e < 5; ++e) lr[e] = dv2(L[2 * e], L[2 * e + 1]);
-        }
-        PT_END(S, 14);
-        if (!ok) return 0;
-        sync();
-        flush_rec(S, Rec, k);
-        if (k == 0) break;
-        // [F] P = Qxx + Qux^T K (upper, mirrored), p = qx + Qux^T k.  Branch-free reads (padding lanes read
-        // entry (0,0)), stores predicated.
-        {
-            // Qux rows (M row i, u block at MU) and K^T rows (kbuf [j][4]) as 16-byte pieces
-            double mq[3], mu4[3][NU], kb[3][NU], vq = 0.0, vu[NU], kk4[NU];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const int i = pi_[r], j = pj_[r];
-                mq[r] = S.M[i * GST + j];
-                const dvec2 *mp = (const dvec2 *)&S.M[i * GST + MU], *kp = (const dvec2 *)&S.kbuf[j * NU];
-                const dvec2 m01 = mp[0], m23 = mp[1], k01 = kp[0], k23 = kp[1];
-                mu4[r][0] = m01.x; mu4[r][1] = m01.y; mu4[r][2] = m23.x; mu4[r][3] = m23.y;
-                kb[r][0] = k01.x; kb[r][1] = k01.y; kb[r][2] = k23.x; kb[r][3] = k23.y;
-            }
-            const int li = min(lane, NA - 1);
-            vq = S.vec[24 + li];
-            {
-                const dvec2 *mp = (const dvec2 *)&S.M[li * GST + MU], *kp = (const dvec2 *)&S.kbuf[NA * NU];
-                const dvec2 m01 = mp[0], m23 = mp[1], k01 = kp[0], k23 = kp[1];
-                vu[0] = m01.x; vu[1] = m01.y; vu[2] = m23.x; vu[3] = m23.y;
-                kk4[0] = k01.x; kk4[1] = k01.y; kk4[2] = k23.x; kk4[3] = k23.y;
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, 64, 0);   // DS reads first
-            __builtin_amdgcn_sched_group_barrier(0x002, 256, 0);  // then VALU
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                double acc = mq[r];
-#pragma unroll
-                for (int a = 0; a < NU; ++a) acc += mu4[r][a] * kb[r][a];
-                // entries past NUP17 (r = 2, lane > 24) recompute P(0,0), which entry 0 also writes
-                S.P[pi_[r] * PST + pj_[r]] = acc;
-                S.P[pj_[r] * PST + pi_[r]] = acc;
-                // unconditional: entries past NUP17 hold P(0,0) and store it to packed slot 0, as entry 0 does
-                Pst[pst_at(k - 1, (r < 2 || lane + 64 * r < NUP17) ? lane + 64 * r : 0)] = acc;
-            }
-            double acc = vq;
-#pragma unroll
-            for (int a = 0; a < NU; ++a) acc += vu[a] * kk4[a];
-            S.p[li] = acc;
-            ws[WS_PVK + (size_t)k * 18 + li] = acc;   // p_k for the costate identity
-        }
-        sync();
-        PT_END(S, 15);
-    }
-    vm_sync();
-    return 1;
-#undef SCATTER_STAGE
 }
 
 // ---- sweeps on the compact record ---------------------------------------------------------------------
@@ -852,7 +477,7 @@ __device__ __attribute__((always_inline)) inline void forward_chain(const Model 
     const double ur = (h == 1 && o >= NX) ? 1.0 : 0.0;
     const double tw0 = -tcy + tcz + ((o == 13) ? ur : 0.0), tw1 = -tcx - tcz + ((o == 14) ? ur : 0.0);
     const double tw2 = tcy + tcz + ((o == 15) ? ur : 0.0), tw3 = tcx - tcz + ((o == 16) ? ur : 0.0);
-    const int dof = o * SX + (o < NX ? 1 : 0);   // dx_{s+1}[o] or du_s[o - 13] (WS_DU follows WS_DX)
+    const int dof = o * SX + (o < NX ? 1 : 0);   // dx_{s+1}[o] or du_s[o - 13] (Smem::du follows Smem::dx)
     if (lane < NA) S.ring[lane] = 0.0;           // x~_0 = 0
     if (lane < NX) DX[lane * SX] = 0.0;
     sync();
@@ -967,13 +592,10 @@ __device__ __attribute__((always_inline)) inline void forward_chain(const Model 
 
 // ---- P_k's packed rows 0..12 (the x rows) as a stream of 16-byte pieces, lane = stage --------------------------
 // f(a, b, P(a, b)) for every packed entry (a, b >= a) of rows a < NX, in packed order.  The pieces go out in blocks of
-// LAFSE3_PB, every load of a block issued before its first use (sched_barrier): left to itself the compiler issued
+// PB = 24, every load of a block issued before its first use (sched_barrier): left to itself the compiler issued
 // four loads at a time and waited for them before the next four, 18 dependent round trips to L2 / MALL per pass
 // (the costates pass took 2.3x its unloaded time in a full launch).  The order of the f calls is the packed order
 // whatever the block size, so every sum built from them is the same FMA chain.
-#ifndef LAFSE3_PB
-#define LAFSE3_PB 24
-#endif
 // issued(): called once, after the last block's loads are issued and before their first use: a caller's own loads
 // placed there return behind the stream's and wait under the last block's arithmetic.
 template <typename F, typename G>
@@ -981,7 +603,7 @@ __device__ __attribute__((always_inline)) inline void p_rows_stream(const gdvec2
 {
     constexpr int NE = up17(NX - 1, NA - 1) + 1;   // entries of rows 0..12
     constexpr int NP = (NE + 1) / 2;               // 16-byte pieces
-    constexpr int PB = LAFSE3_PB;
+    constexpr int PB = 24;
 #pragma unroll
     for (int q0 = 0; q0 < NP; q0 += PB) {
         dvec2 buf[PB];

@@ -1,11 +1,23 @@
 // riccati_mfma.inc — the factorisation sweep (backward sweep of the Riccati solve) on the f64 matrix cores
 // (included by ipm_kernel.hip after riccati.inc).
 //
-// Same Newton system and the same outputs as backward_full (riccati.inc): the factor record K_k^T, k_k, L_k
-// (WS_REC), P_k packed (WS_PST) and p_k (WS_PVK) of every stage, in the x~ = [r v q w u~] order the chains read.
-// The stage is the value-function update of the multiple-shooting NLP of quad_OC.py:124-167 (Δu term
-// quad_OC.py:145-151 -> the u~ = u_{k-1} augmentation):
-//   W = P G,  M = G^T W + H~,  K = -Quu^{-1} Qux,  k = -Quu^{-1} g_u,  P' = Qxx + Qux^T K,  p' = g_x + Qux^T k
+// The Newton system is the stage QP of riccati.inc's header (stage table of build_table: G_k, H~_k, h~_k, c~_k).  The
+// sweep runs k = N-1 .. 0, sequential over k with the wave's 64 lanes on one stage, from the terminal value function
+// P_N, p_N (riccati.inc terminal).  A stage is the value-function update of the multiple-shooting NLP of
+// quad_OC.py:124-167 (Δu term quad_OC.py:145-151 -> the u~ = u_{k-1} augmentation), in four phases (the letters
+// name them in the comments and the phase timers):
+//   [C]  W = P G                                      (P = P_{k+1}; with it the gradient's ph = p + P c~)
+//   [D]  M = G^T W + H~ (+ delta_w on the flagged diagonal),  g = G^T ph + h~;  M = [[Qxx, Qxu], [Qux, Quu]]
+//   [E]  Cholesky of Quu (4 x 4; a pivot that is not positive is wrong inertia),  K = -Quu^{-1} Qux,  k = -Quu^{-1} g_u
+//   [F]  P' = Qxx + Qux^T K,  p' = g_x + Qux^T k      (P_k, p_k: the next stage's P, p)
+// Outputs, in the x~ = [r v q w u~] order the chains read:
+//   * the factor record of every stage k = 0..N-1 (WS_REC, REC doubles: K_k^T [j][4] at RC_K, k_k at RC_KF, the packed
+//     factor L_k of Quu_k at RC_L with 1 / l_jj in its diagonal slots),
+//   * P_k packed (upper triangle of the 17 x 17, NUP17 entries at stride PSTR) in slot k - 1 of WS_PST for k = 1..N
+//     (terminal stores P_N),
+//   * p_k at WS_PVK + 18 k for k = 1..N-1 (p_N: WS_PN, the x rows),
+//   * the return value: 1, or 0 when some Quu_k is not positive definite (wrong inertia); the outputs of a failed
+//     sweep are partial and the caller retries with another delta_w, which overwrites them.
 //
 // MFMA order.  The 17 x~ entries are taken as m = 0..15 <-> x~ index m + 1 (r1 r2 v q w u~) and m = 16 <-> r0,
 // the 17 active G columns likewise (m = 0..11 <-> x 1..12, 12..15 <-> u, 16 <-> r0).  r0 enters the dynamics only
@@ -25,10 +37,10 @@
 //   * vectors indexed by x~ "row-group" (lane holds v[4s + g], s = 0..3) or "column" (lane holds v[c]); the one
 //     transposition per stage (p12', p' column -> row-group) goes through 32 doubles of LDS.
 //   * Quu (M11 rows / columns 12..15) and the r0 / g_u right-hand sides are read with v_readlane: the 4 x 4
-//     Cholesky (inertia test) is the wave-uniform chain of riccati.inc [E].
+//     Cholesky (inertia test) of [E] is a wave-uniform chain, the same in every lane.
 // The f64 matrix core shares the FP64 pipeline with the VALU on gfx950 (tools/ubench_mfma.hip: an MFMA and
 // independent v_fma_f64 do not overlap), so the gain is instruction count: 4 MFMAs form a dense 16 x 16 x 16
-// product that the VALU stage formed from ~60 FMAs plus the LDS exchanges around them.
+// product that takes ~60 FMAs per lane on the VALU, plus the LDS exchanges around them.
 
 typedef double d4v __attribute__((ext_vector_type(4)));
 
@@ -36,7 +48,7 @@ __device__ inline d4v mfma64(double a, double b, d4v c) { return __builtin_amdgc
 
 // 1 / sqrt(d) for the pivot chain: v_rsq_f64 (relative error <= 2^-23) and one third-order correction,
 // y + y r (1/2 + 3 r / 8) with r = 1 - d y^2 (error O(r^3) < 2^-64): four dependent operations after the rsq where
-// rsqrt_nr's two Newton steps take six.  d <= 0 gives NaN, and the stage returns "wrong inertia" before any of it
+// two Newton steps take six.  d <= 0 gives NaN, and the stage returns "wrong inertia" before any of it
 // is stored.
 __device__ inline double rsqrt_chol(double d)
 {
@@ -81,8 +93,8 @@ __host__ __device__ constexpr int mf_x(int m) { return m + 1; }                 
 __host__ __device__ constexpr int mf_z(int m) { return (m + 1) < NX ? (m + 1) : (m + 1) + NU; }  // m -> z index
 constexpr int MF_ZERO = -1;
 
-// table slot of G(x~ row R, z column z): a stage-dependent slot, a per-row constant (TB_K, init_gv_const's
-// values) or a structural zero
+// table slot of G(x~ row R, z column z): a stage-dependent slot, a per-row constant (TB_K: the identity entries, dt and
+// the rotor torque map, which build_table writes into every row) or a structural zero
 __host__ __device__ constexpr int mf_gsrc(int R, int z)
 {
     for (int t = 0; t < GLEN; ++t) {
@@ -224,7 +236,7 @@ static_assert(mf_flags_are_diagonal(), "delta_w flags of the MFMA stage: the dia
 #define PT_FINE(i) ((void)0)
 #endif
 
-// Returns 1 on success, 0 when some Quu is not positive definite (wrong inertia), as backward_full.
+// Returns 1 on success, 0 when some Quu is not positive definite (wrong inertia).
 __device__ __attribute__((always_inline)) inline int backward_mfma(const Model &M, const Attitude &at, Smem &S, const Ctl &C,
                                                                    gdouble *ws, double dw, int mode_lsq)
 {
@@ -396,7 +408,7 @@ __device__ __attribute__((always_inline)) inline int backward_mfma(const Model &
         // Qxx's x block transposed through LDS (consumed only by [F], under the pivot chain's latency): [F]'s C operand
         // is (M + M^T) / 2, so that P' = C - Y^T Y comes out of the MFMA symmetric bit for bit (M = G^T (P G) is not,
         // and a P whose halves differ by rounding lost accuracy on the ill-conditioned delta_w = 0 systems of the IFT
-        // mode: tools/fac_check.py, tests/test_gpu_parity.py::test_sol_gradient_ift_mode_matches_oracle)
+        // mode: tests/test_gpu_parity.py::test_sol_gradient_ift_mode_matches_oracle)
         {
             double *T = L0 + MF_TR;
 #pragma unroll

@@ -18,7 +18,6 @@ namespace lafse3 {
 constexpr int GLEN = 7;     // entries per G column list
 constexpr int NGV = 54;     // stage-dependent G slots
 constexpr int NHV = 62;     // upper-triangle nonzeros of H~
-constexpr int NUP = 231;    // upper triangle of a 21 x 21
 constexpr int NUP17 = 153;  // upper triangle of a 17 x 17
 
 // stage table layout (doubles per stage)
@@ -90,7 +89,6 @@ __host__ __device__ constexpr HTab make_htab()
 }
 
 struct UpTab {
-    unsigned char i[NUP], j[NUP];
     unsigned char i17[NUP17], j17[NUP17];
 };
 
@@ -98,13 +96,6 @@ __host__ __device__ constexpr UpTab make_uptab()
 {
     UpTab T{};
     int n = 0;
-    for (int i = 0; i < 21; ++i)
-        for (int j = i; j < 21; ++j) {
-            T.i[n] = (unsigned char)i;
-            T.j[n] = (unsigned char)j;
-            ++n;
-        }
-    n = 0;
     for (int i = 0; i < 17; ++i)
         for (int j = i; j < 17; ++j) {
             T.i17[n] = (unsigned char)i;

@@ -12,9 +12,8 @@
 // columns directly (sens_contract's gx0).
 //
 // The point comes from the record ipm_kernel_ext stored (REC_*), not from a solve on this wave: the instance prologue
-// of run_instance (Model and the weight row, attitude forms, S.wk, relaxed bounds, init_gv_const, goal / p_tra /
-// u_last) is repeated here from the same arguments, then x, u, the scaled lam, the bound duals, mu and the objective
-// scaling are loaded.
+// of run_instance (Model and the weight row, attitude forms, S.wk, relaxed bounds, goal / p_tra / u_last) is repeated
+// here from the same arguments, then x, u, the scaled lam, the bound duals, mu and the objective scaling are loaded.
 constexpr int VJP_HORIZON = 3;   // sens_status: the record's horizon is not the context's
 
 struct VjpArgs {
@@ -59,7 +58,6 @@ __device__ __attribute__((always_inline)) inline void vjp_instance(const VjpArgs
             w_peak = uniform(w[W_PEAK]);
             w_decay = uniform(w[W_DECAY]);
         }
-        init_gv_const(M, S);
         WS_TRAJ(ws);
         // Whatever the contraction at the end reads of this prologue is wave-uniform and kept in SGPRs (uniform()), or
         // in LDS: the loops below retire their lanes one by one, and the compiler has parked vector registers that
@@ -83,9 +81,6 @@ __device__ __attribute__((always_inline)) inline void vjp_instance(const VjpArgs
         C.mu = uniform(rec[REC_MU]);
 #ifdef LAFSE3_PHASE_TIMERS
         S.timing = 0;
-#endif
-#ifdef LAFSE3_FAC_CHECK
-        if (lane < 4) S.facd[lane] = 0.0;
 #endif
         if (lane < 3) {
             S.goal[lane] = A.goal[inst * 3 + lane];

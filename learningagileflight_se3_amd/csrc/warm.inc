@@ -17,8 +17,8 @@
 //   warm_load_duals    after the objective scaling s_new of the loaded point is known: the record's multipliers belong
 //                      to the problem scaled by s_rec, so lam = lam_rec (s_new / s_rec) and
 //                      z = max(z_rec (s_new / s_rec), mult_bound_push).
-// The filter needs no reset (nfilt = 0 at the start of every solve); S.P, S.W, S.M and the refinement arrays of the
-// workspace are written by each linear_solve before it reads them, as after a cold fill.
+// The filter needs no reset (nfilt = 0 at the start of every solve); S.P, the sweeps' scratch in Smem's W / M union
+// and the refinement arrays of the workspace are written by each linear_solve before it reads them, as after a cold fill.
 
 // third argument of ipm_kernel_warm.  Not part of KernelArgs or ExtArgs, as RestoDumpArgs.
 struct WarmArgs {

@@ -19,7 +19,7 @@ offsets the sweep used to compute from the lane index, at every horizon.
  3. Both gradient kernels.  sol_gradient on 8 samples (synthetic_batch(8, seed=7)), FD and grad_mode = 1, twice on one
     context: out8, rewards9 and status9 of the second launch equal the first's bit for bit, and every solve converged.
 
-The tables share no storage with another phase (the restoration phase's scratch is gv / hv / hh / cc, untouched), so
+The tables share no storage with another phase (the restoration phase's scratch is hv / hh / cc, untouched), so
 there is no rebuild to test after a restoration entry.
 """
 import numpy as np

@@ -46,7 +46,7 @@ for step in "$@"; do
     quick)     timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra > gpurun_out/bench_quick.json 2> gpurun_out/bench_quick.err ;;
     moving)    timeout -k 10 600 python bench.py --workload moving --batch 8192 --plant-steps 500 --steps 1 --warmup 1 > gpurun_out/bench_moving.json 2> gpurun_out/bench_moving.err ;;
     facbench)  : > gpurun_out/facbench.log
-               for v in ${VARIANTS:-VF0 VF1}; do
+               for v in ${VARIANTS:-VF1}; do
                  LAFSE3_LIB=$L/liblafse3_$v.so timeout -k 10 120 python tools/facbench.py ${B:-8192} >> gpurun_out/facbench.log 2>&1 || exit $?
                done ;;
     variants)  ROUNDS=${ROUNDS:-2} bash tools/gpu_variants.sh > gpurun_out/variants_summary.log 2>&1 ;;

@@ -14,7 +14,8 @@ cost, status, iters, sens_status or rec differ anywhere.
 
 ab: bench.py's configs[1] batch (scenario.synthetic_batch(B, seed=77), B = 1024 and 8192 as tools/gpu_vjp.py):
 lafse3_last_kernel_ms of ocp_sensitivity (dx, du), ocp_sensitivity_ex (all groups, dx, du, gain) and ocp_solve_rec,
-parent and candidate alternating for five rounds, each round a process that warms every call up once before timing it.
+and ocp_vjp (all groups, on that process's own record) between two events on the launch stream; parent and candidate
+alternating for five rounds, each round a process that warms every call up once before timing it.
 Medians, per-round values, and the bar: the candidate's median may exceed the parent's by the parent's max - min."""
 import json
 import os
@@ -85,6 +86,19 @@ def child_ab(out):
                 ok = int((r["status"] <= 1).sum())
                 del r
             res["B%d %s" % (B, name)] = [eng.last_kernel_ms(), ok]
+        # vjp_kernel is no solver launch (it keeps the last solver launch's timing): two events on the launch stream,
+        # as tools/gpu_vjp.py
+        rec = eng.ocp_solve_rec(*a, want=("x", "u"))
+        g = torch.Generator(device="cuda").manual_seed(7)
+        g_x = torch.randn(B, eng.horizon + 1, 13, dtype=torch.float64, device="cuda", generator=g)
+        g_u = torch.randn(B, eng.horizon, 4, dtype=torch.float64, device="cuda", generator=g)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            ev0.record()
+            v = eng.ocp_vjp(*a, None, None, rec["rec"], g_x, g_u)
+            ev1.record()
+            torch.cuda.synchronize()
+        res["B%d ocp_vjp" % B] = [ev0.elapsed_time(ev1), int((v["sens_status"] == 0).sum())]
     with open(out, "w") as fh:
         json.dump(res, fh)
 
@@ -143,7 +157,7 @@ def ab(parent, cand):
         verdict = "within" if dm <= spread else "EXCEEDS"
         miss += dm > spread
         print("[%s] parent median %.3f ms %s | candidate median %.3f ms %s | difference %+.3f ms, parent spread %.3f ms: %s"
-              " | instances with status <= 1: %s" % (k, np.median(p), [round(v, 3) for v in p], np.median(c),
+              " | instances ok: %s" % (k, np.median(p), [round(v, 3) for v in p], np.median(c),
                                                      [round(v, 3) for v in c], dm, spread, verdict, okc))
     return 1 if miss else 0
 

@@ -40,4 +40,4 @@ for label, batch in (("small", 64), ("full", int(os.environ.get("BIG", "2048")))
           " %.2f %% of all instance cycles (probe cost removed)" %
           (W[0] / nst, W[1] / nst, W[7] / max(1.0, nst * ((W[0] > 0) + (W[1] > 0))),
            100.0 * max(0.0, W[0] + W[1] - W[7]) / T.sum()))
-    print("   backward_full per stage (ticks): [A] %.0f  [C+D] %.0f  [E] %.0f  [F] %.0f" % tuple(X)); print("   slot5 %.0f  slot10 %.0f per stage (diagnostic splits)" % tuple(T.sum(0)[[5, 10]] / (cnt["iterations"] + batch) / 50))
+    print("   factorisation stage (ticks): entry + row loads %.0f  [C+D] %.0f  [E] %.0f  [F] %.0f" % tuple(X)); print("   slot5 %.0f  slot10 %.0f per stage (diagnostic splits)" % tuple(T.sum(0)[[5, 10]] / (cnt["iterations"] + batch) / 50))

@@ -1,5 +1,6 @@
-"""Sub-phase cycles of the MFMA factorisation stage (timer build with -DLAFSE3_PT_FINE, given by LAFSE3_LIB):
-slots 12..15 ([A] [C+D] [E] [F]) and the fine markers 16..23 of riccati_mfma.inc, ticks per stage."""
+"""Sub-phase cycles of the factorisation stage, riccati_mfma.inc backward_mfma (timer build with -DLAFSE3_PT_FINE, given
+by LAFSE3_LIB): slots 12..15 (stage entry and row loads, [C] + [D], [E], [F]) and the fine markers 16..23, ticks per
+stage."""
 import os
 import sys
 
